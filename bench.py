@@ -20,12 +20,19 @@ skipped or cached between steps.
   cpu_baseline = the oracle (CPU restatement of the reference, bit-identical to it) timed on this
                box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
 
+A plain run sets up, warms up, times the --steps steps and prints the line: `value`, `ms_per_step`,
+`step_ms` and the `roofline` of the panel launches of the timed steps.  Everything that takes work
+of its own — the eigenvalue check, `stream_read`, the standalone launch, `general_k1`, `weak_extra`,
+`multi_gpu`, `cpu_baseline` and the `configs` block — runs only with --full (the --no-* options
+then drop single parts of it).  --dump-outputs DIR writes what the last timed step returned
+(eigenvalues and eigenvectors of the whole batch) as DIR/<name>.npy.
+
 Multi-GPU: `python bench.py --gpus N` re-executes itself under torch.distributed.run (one rank per
 GPU, RCCL); launched by torch.distributed.run directly it just runs.  The batched-operator dimension
-is sharded.  Default = STRONG scaling of the metric's batch of 64 (64/N operators per GPU); a short
-weak-scaled run (64 operators per GPU) follows outside the timed region and is reported as
-`weak_extra`.  The only exchange is the per-iteration all-reduce(MAX) of {residual, flag} (RCCL),
-which keeps the reference's global stopping rule.
+is sharded.  Default = STRONG scaling of the metric's batch of 64 (64/N operators per GPU); with
+--full a short weak-scaled run (64 operators per GPU) follows outside the timed region and is
+reported as `weak_extra`.  The only exchange is the per-iteration all-reduce(MAX) of {residual, flag}
+(RCCL), which keeps the reference's global stopping rule.
 """
 import argparse
 import json
@@ -52,8 +59,12 @@ def parse():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="strong (default): --batch operators in total, split over the GPUs; weak: --batch per GPU")
-    ap.add_argument("--no-weak-extra", action="store_true", help="N > 1: skip the short weak-scaled extra run")
-    ap.add_argument("--no-general-extra", action="store_true", help="skip the extra run with the full-matrix kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every check and extra measurement (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-weak-extra", action="store_true", help="--full, N > 1: skip the short weak-scaled extra run")
+    ap.add_argument("--no-general-extra", action="store_true", help="--full: skip the extra run with the full-matrix kernel")
     ap.add_argument("--max-niter", type=int, default=200, help="guard only; ~19 iterations are needed")
     ap.add_argument("--no-overlap", action="store_true",
                     help="one batch group on one stream (default: two groups, panel products on a CU-masked stream)")
@@ -79,17 +90,41 @@ def parse():
     ap.add_argument("--cfg-batch", type=int, default=0, help="--config: operators / systems per GPU (0 = the config's own)")
     ap.add_argument("--gmres-restart", type=int, default=0, help="--config c3g: restarted GMRES(m) (0 = un-restarted)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` block (the other BASELINE.json configs, measured after the headline: c0 N=512 "
-                         "symeig, c3 BiCGStab fwd+bwd, c4 Broyden shard, c5w fp32 16-column shard; each with its roofline and "
-                         "a CPU baseline)")
+                    help="--full: skip the `configs` block (the other BASELINE.json configs, measured after the headline: c0 "
+                         "N=512 symeig, c3 BiCGStab fwd+bwd, c4 Broyden shard, c5w fp32 16-column shard; each with its roofline "
+                         "and a CPU baseline)")
     ap.add_argument("--cfg-steps", type=int, default=5, help="timed steps of every entry of the `configs` block")
     ap.add_argument("--no-standalone", action="store_true",
-                    help="skip the stream-read / standalone whole-batch launches after the timed region (profiled runs: the "
-                         "trace then holds the timed region's panel launches only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the stream-read / standalone whole-batch launches after the timed region (profiled "
+                         "runs: the trace then holds the timed region's panel launches only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", default="4x4096", help="BxN of the CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=32)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: at most this many bytes in all
+
+
+def _dump_outputs(path, arrays):
+    """--dump-outputs: write every (name, numpy array) as path/<name>.npy, float32 / float64 as computed.  At most one
+    array has three dimensions (the eigenvectors, (B, N, p)); if it would take the total beyond DUMP_BYTES it is cut to
+    a fixed, seeded sample of rows along dimension 1, whose indices are written beside it as <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES - 4096 - sum(a.nbytes for _, a in arrays if a.ndim != 3)      # (4096: the .npy headers)
+    for name, a in arrays:
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        if a.ndim == 3 and a.nbytes > budget:
+            keep = budget // (a.nbytes // a.shape[1] + 8)           # + 8: the float64 row index of each kept row
+            rows = np.sort(np.random.default_rng(12421).choice(a.shape[1], size=keep, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[:, rows, :]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(args):
@@ -431,7 +466,7 @@ def main_dry(args):
         if group is not None:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        run.local_elapsed = elapsed
+        run.local_elapsed, run.last_y = elapsed, y
         if group is not None:
             tt = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -446,9 +481,19 @@ def main_dry(args):
 
     b_local, b_total, offset = shard(args.scaling)
     elapsed, fmax, tr = run(b_local, offset, args.steps, args.warmup)
-    multi_gpu = _multi_gpu_diag(group, torch.device("cpu"), run.local_elapsed, None, args.steps) if group is not None else None
+    if args.dump_outputs:
+        y = run.last_y.numpy()
+        if group is not None:                    # (shards may differ in size here)
+            parts = [None] * world
+            dist.all_gather_object(parts, y)
+            y = torch.cat([torch.from_numpy(p) for p in parts]).numpy()
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, [("root", y)])
+    multi_gpu = None
+    if group is not None and args.full:
+        multi_gpu = _multi_gpu_diag(group, torch.device("cpu"), run.local_elapsed, None, args.steps)
     weak_extra = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_extra:
+    if world > 1 and args.scaling == "strong" and args.full and not args.no_weak_extra:
         wl, wt, woff = shard("weak")
         w_el, _, _ = run(wl, woff, 2, 1)
         weak_extra = {"scaling": "weak", "value": None, "ms_per_step": w_el / 2 * 1e3, "global_batch": wt,
@@ -548,7 +593,6 @@ def main():
     dtype = torch.float64 if args.dtype == "f64" else torch.float32
     esize = 8 if args.dtype == "f64" else 4
     N, p = args.n, args.neig
-    exact = synthetic.spectrum(args.spectrum, N, torch.float64, dev)[:p]
 
     def fence():
         if group is not None:
@@ -604,6 +648,7 @@ def main():
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             elapsed = tt.item()
         step_ms = [round((b - a) * 1e3, 2) for a, b in zip([t0] + marks[:-1], marks)]
+        run.last_evecs = evecs
         return elapsed, evals, traces, step_ms
 
     def shard(scaling):
@@ -618,42 +663,62 @@ def main():
     symm = bool(A.symmetric_storage)
     k1_events = []
     elapsed, evals, traces, step_ms = run(A, args.steps, args.warmup, k1_events)
-
-    # result checks (outside the timed region)
-    tol = 1e-10 if dtype == torch.float64 else 1e-3
-    eval_err = (evals.double() - exact).abs().max().item()
-    resid = traces[-1]["best_resid"]
-    ok = eval_err <= tol * 100.0 and resid < args.min_eps
     roofline, durs = _k1_roofline(k1_events, N, p, esize, symm, b_local)
-    multi_gpu = None
-    if group is not None:
-        multi_gpu = _multi_gpu_diag(group, dev, run.local_elapsed, (sum(durs) / len(durs)) if durs else None, args.steps)
+
+    if args.dump_outputs:
+        # what the last timed step returned, whole batch (ranks' shards gathered in batch order); outside the timed region
+        outs = [("eigenvalues", evals), ("eigenvectors", run.last_evecs)]
+        if group is not None:
+            gathered = []
+            for name, t in outs:
+                parts = [torch.empty_like(t) for _ in range(world)]
+                torch.distributed.all_gather(parts, t.contiguous(), group=group)
+                gathered.append((name, torch.cat(parts)))
+            outs = gathered
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, [(name, t.cpu().numpy()) for name, t in outs])
+        del outs
+    run.last_evecs = None
+
+    check, multi_gpu = None, None
+    if args.full:
+        # result checks (outside the timed region)
+        exact = synthetic.spectrum(args.spectrum, N, torch.float64, dev)[:p]
+        tol = 1e-10 if dtype == torch.float64 else 1e-3
+        eval_err = (evals.double() - exact).abs().max().item()
+        resid = traces[-1]["best_resid"]
+        check = {"ok": bool(eval_err <= tol * 100.0 and resid < args.min_eps), "max_eval_err_vs_exact": eval_err,
+                 "max_resid": resid}
+        if group is not None:
+            multi_gpu = _multi_gpu_diag(group, dev, run.local_elapsed, (sum(durs) / len(durs)) if durs else None,
+                                        args.steps)
 
     # ---------------- extra: the timed kernel alone on the GPU (no other batch group beside it) ----------------
     # inside the two-group pipeline the panel product shares HBM with the other group's small kernels (that is the
     # point of the pipeline); the same kernel on the whole batch with nothing else running shows what the sharing costs
     # what the operator batch streams at with no arithmetic at all (3 read-only passes, idle GPU): the practical
     # ceiling of any panel kernel on this box and this placement of the batch
-    try:
-        if args.no_standalone:
-            raise RuntimeError("skipped (--no-standalone)")
-        XK.stream_read(mat)
-        re_ = []
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            nread = XK.stream_read(mat)
-            e1.record()
-            re_.append((e0, e1))
-        torch.cuda.synchronize()
-        r_avg = sum(a.elapsed_time(b) for a, b in re_) / len(re_) * 1e-3
-        roofline["stream_read"] = {"GBps": nread / r_avg / 1e9, "frac_of_peak": nread / r_avg / 1e9 / 8000.0,
-                                   "bytes": nread, "avg_ms": r_avg * 1e3,
-                                   "note": "xk_stream_read over the whole operator batch: 16 B/lane nt loads, no arithmetic"}
-        roofline["frac_of_stream_read"] = roofline["achieved"] / roofline["stream_read"]["GBps"]
-    except Exception as err:        # a measurement extra never costs the headline line
-        roofline["stream_read"] = {"error": repr(err)}
-    if symm and not args.no_standalone:
+    if args.full:
+        try:
+            if args.no_standalone:
+                raise RuntimeError("skipped (--no-standalone)")
+            XK.stream_read(mat)
+            re_ = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                nread = XK.stream_read(mat)
+                e1.record()
+                re_.append((e0, e1))
+            torch.cuda.synchronize()
+            r_avg = sum(a.elapsed_time(b) for a, b in re_) / len(re_) * 1e-3
+            roofline["stream_read"] = {"GBps": nread / r_avg / 1e9, "frac_of_peak": nread / r_avg / 1e9 / 8000.0,
+                                       "bytes": nread, "avg_ms": r_avg * 1e3,
+                                       "note": "xk_stream_read over the whole operator batch: 16 B/lane nt loads, no arithmetic"}
+            roofline["frac_of_stream_read"] = roofline["achieved"] / roofline["stream_read"]["GBps"]
+        except Exception as err:        # a measurement extra never costs the headline line
+            roofline["stream_read"] = {"error": repr(err)}
+    if symm and args.full and not args.no_standalone:
         Xs = torch.randn((b_local, p, N), dtype=dtype, device=dev)
         Ys = torch.empty_like(Xs)
         XK.dense_symm(mat, Xs, out=Ys)
@@ -678,7 +743,7 @@ def main():
 
     # ---------------- extra: the full-matrix panel kernel on the same resident operator ----------------
     general = None
-    if symm and not args.no_general_extra:
+    if symm and args.full and not args.no_general_extra:
         A.symmetric_storage = False
         gev = []
         g_el, g_evals, g_tr, g_ms = run(A, max(1, min(args.steps, 10)), 1, gev)     # (10 x 0.4 s: VERDICT r03 #6)
@@ -697,7 +762,7 @@ def main():
                     "workload on the full-matrix kernel K1 (what an operator whose storage is not exactly symmetric gets), "
                     "timed the same way after the headline's timed region; `frac` above prices the upper-triangle kernel "
                     "on the bytes IT must move"}
-    elif not symm:
+    elif not symm and args.full:
         # one whole-batch launch of the general kernel, timed alone (untimed region), bytes of the WHOLE batch
         Xg = torch.randn((b_local, p, N), dtype=dtype, device=dev)
         Yg = torch.empty_like(Xg)
@@ -717,7 +782,7 @@ def main():
 
     # ---------------- extra: weak scaling (64 operators per GPU), N > 1 only ----------------
     weak_extra = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_extra:
+    if world > 1 and args.scaling == "strong" and args.full and not args.no_weak_extra:
         del A, mat
         torch.cuda.empty_cache()
         try:
@@ -752,7 +817,7 @@ def main():
             "weak_extra": weak_extra,
             "multi_gpu": multi_gpu,
             "matvec_fraction_of_step": sum(durs) / elapsed if elapsed > 0 else None,
-            "check": {"ok": bool(ok), "max_eval_err_vs_exact": eval_err, "max_resid": resid},
+            "check": check,
             "step_ms": step_ms,
             "k1_ms_first_last": [round(durs[0] * 1e3, 3), round(durs[-1] * 1e3, 3)] if durs else None,
             "k1_ms_last_step": [round(d * 1e3, 2) for d in durs[-2 * traces[-1]["niter"]:]] if durs else None,
@@ -760,9 +825,9 @@ def main():
                                     "batch groups alternate; the basis grows by 6 vectors per pair, and with it the bytes "
                                     "the other group's chain moves beside the launch)",
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             try:
                 del A, mat
             except NameError:

@@ -9,7 +9,7 @@ if [ "$1" != "nobtests" ]; then
 fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt
 SECONDS=0
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2>$O/bench_err.txt; echo "bench wall seconds: $SECONDS" | tee $O/bench_wall.txt; tail -1 $O/bench_err.txt
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line.json 2>$O/bench_err.txt; echo "bench wall seconds: $SECONDS" | tee $O/bench_wall.txt; tail -1 $O/bench_err.txt
 python - <<PY
 import json
 d = json.loads(open("$O/bench_line.json").read().strip().splitlines()[-1])

@@ -10,14 +10,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.timeout(300)
-@pytest.mark.parametrize("gpus,batch", [(2, 5), (1, 3)])
-def test_bench_dry_run_prints_one_json_line(gpus, batch):
+def _dry_run(gpus, batch, *extra):
+    """`bench.py --gpus <gpus> --dry-run --steps 2 --warmup 1 --batch <batch> <extra>`: the one JSON line rank 0 prints"""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-run", "--steps", "2", "--warmup", "1",
-           "--batch", str(batch)]
+           "--batch", str(batch)] + list(extra)
     for attempt in range(2):
         proc = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=140, cwd=ROOT)
         # (gloo's own teardown aborts once in a long while on a loaded box — "terminate called without an active
@@ -27,7 +26,13 @@ def test_bench_dry_run_prints_one_json_line(gpus, batch):
     assert proc.returncode == 0, proc.stderr.decode()[-2000:]
     lines = [ln for ln in proc.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines                          # rank 0 prints exactly one line, nobody else anything
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("gpus,batch", [(2, 5), (1, 3)])
+def test_bench_dry_run_prints_one_json_line(gpus, batch):
+    d = _dry_run(gpus, batch, "--full")
     assert d["dry_run"] is True and d["value"] is None and d["roofline"] is None
     assert d["n_gpus"] == gpus and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "strong"
     assert d["config"]["global_batch"] == batch and d["config"]["comm_world_size"] == gpus
@@ -44,6 +49,47 @@ def test_bench_dry_run_prints_one_json_line(gpus, batch):
         assert w["global_batch"] == batch * gpus and w["batch_per_gpu"] == batch
     else:
         assert d["weak_extra"] is None
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_dry_run_skips_the_extras_and_dumps_the_same_outputs_on_any_shard_count(tmp_path):
+    """Without --full the line carries the headline only (no weak-scaled run, no per-rank diagnostics); --dump-outputs
+    writes what the last timed step returned, gathered over the ranks: the same arrays from one rank and from two."""
+    import numpy as np
+    d2 = _dry_run(2, 5, "--dump-outputs", str(tmp_path / "two"))
+    d1 = _dry_run(1, 5, "--dump-outputs", str(tmp_path / "one"))
+    for d in (d1, d2):
+        assert d["steps"] == 2 and d["ms_per_step"] > 0.0 and d["check"]["ok"]
+        assert d["weak_extra"] is None and d["multi_gpu"] is None
+    y2, y1 = np.load(tmp_path / "two" / "root.npy"), np.load(tmp_path / "one" / "root.npy")
+    assert y2.dtype == np.float64 and y2.shape == (5, 24)
+    assert np.array_equal(y1, y2)
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_rows_beyond_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs stays within bench.DUMP_BYTES: the (B, N, p) eigenvectors are cut to a seeded, sorted sample of rows
+    (indices beside them), the same on every run; arrays within the budget are written whole; only float32 / float64."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(0)
+    evals, evecs = rng.standard_normal((4, 6)), rng.standard_normal((4, 1000, 6)).astype(np.float32)
+    bench._dump_outputs(str(tmp_path / "whole"), [("eigenvalues", evals), ("eigenvectors", evecs)])
+    assert np.array_equal(np.load(tmp_path / "whole" / "eigenvectors.npy"), evecs)
+    assert not (tmp_path / "whole" / "eigenvectors_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + evals.nbytes + 100 * (4 * 6 * 4 + 8))
+    for run in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / run), [("eigenvalues", evals), ("eigenvectors", evecs)])
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["eigenvalues.npy", "eigenvectors.npy", "eigenvectors_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    rows = np.load(tmp_path / "a" / "eigenvectors_rows.npy")
+    sample = np.load(tmp_path / "a" / "eigenvectors.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert sample.dtype == np.float32 and np.array_equal(sample, evecs[:, rows.astype(np.int64), :])
+    assert np.array_equal(np.load(tmp_path / "b" / "eigenvectors_rows.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "eigenvalues.npy"), evals)
+    with pytest.raises(TypeError):
+        bench._dump_outputs(str(tmp_path / "c"), [("counts", np.arange(3))])
 
 
 def test_panel_launch_periods_split_overlapping_intervals():
