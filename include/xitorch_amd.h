@@ -476,6 +476,47 @@ int xk_cg_p_c128(const double* z, double* p, const double* Prz_new, const double
 int xk_cg_p_c64(const float* z, float* p, const float* Prz_new, const float* Prz_old, int S, int N, long ld, int nblk,
                 double eps, void* stream);
 
+/* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
+ * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
+ * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.
+ * Pointers address INTERLEAVED (re, im) storage; every stride and length counts COMPLEX elements; lam is real.
+ * The tall products (V^H W, V C, V^H AW, W^H AW) run on the real K1 kernels through the interleaved storage.
+ *
+ * xk_herm_eigh: lowest (uppest = 0) / uppermost p eigenpairs of the Hermitian T[b] (B, k, k), lower triangle read,
+ *   imaginary part of the diagonal ignored: lam (B, p) ascending, Y (B, p, k) with Y[b, j] the j-th eigenvector,
+ *   info[b] = 1 when the self-check failed (tridiagonal residuals, orthonormality, scale range 2^-450 .. 2^450 for
+ *   c128 / 2^-50 .. 2^50 for c64): repeat that member on a library eigh.  Householder reduction to a REAL symmetric
+ *   tridiagonal (reflectors chosen so that the sub-diagonal is real), bisection, inverse iteration,
+ *   back-transformation.  One workgroup per matrix, packed triangle in LDS.  Limits: 1 <= p <= 16, p <= k <= 128
+ *   (both types; xk_herm_eigh_lds_bytes(k, p, 8 | 4) <= 160 KiB).  ws: xk_herm_eigh_workspace_elems(B, k, p)
+ *   real elements (inverse-iteration factors), ws_elems its size.
+ * xk_herm_ritz: X = Y^T V, Tn = -R with R = Y^T AV - diag(lam) Y^T MV (MV = NULL: V), status[1 + b] = max |R_b|
+ *   (complex modulus) and status[0] = max over b; status (B + 1 doubles) is zeroed by the call, the maxima are integer
+ *   maxima of the bit patterns (order-independent, a NaN propagates).  V, AV, MV: (B, >= k, ld) panels; Y (B, k, p)
+ *   with strides (sY, sYa, sYc); lam (B, p) with unit stride along p.  V / AV / MV are read once per 16 columns.
+ * xk_herm_cholqr: CholeskyQR of the q-vector block W (B, q, ld) in the (M-)inner product, in place:
+ *   G = W^H MW (MW = NULL: W), fixed summation order (bit-reproducible), G + shift_rel trace(G) I = R^H R,
+ *   W <- W R^-1 and MW <- MW R^-1; Rinv: scratch of B q q complex elements (holds R^-1 afterwards).  info[b] =
+ *   index + 1 of the first non-positive pivot if info[b] was 0 (sticky; the pivot is then taken as 1).  q <= 32. */
+long xk_herm_eigh_lds_bytes(int k, int p, int elem_size);
+long xk_herm_eigh_workspace_elems(int B, int k, int p);
+int xk_herm_eigh_c128(const double* T, double* lam, double* Y, int* info, double* ws, long ws_elems, int B, int k,
+                      int p, int uppest, long ldt, long sT, void* stream);
+int xk_herm_eigh_c64(const float* T, float* lam, float* Y, int* info, float* ws, long ws_elems, int B, int k, int p,
+                     int uppest, long ldt, long sT, void* stream);
+int xk_herm_ritz_c128(const double* V, const double* AV, const double* MV, const double* Y, const double* lam,
+                      double* X, double* Tn, double* status, int B, int k, int N, int p, long ldv, long sV, long ldav,
+                      long sAV, long ldmv, long sMV, long sY, long sYa, long sYc, long sL, long ldx, long sX,
+                      long ldtn, long sTn, void* stream);
+int xk_herm_ritz_c64(const float* V, const float* AV, const float* MV, const float* Y, const float* lam, float* X,
+                     float* Tn, double* status, int B, int k, int N, int p, long ldv, long sV, long ldav, long sAV,
+                     long ldmv, long sMV, long sY, long sYa, long sYc, long sL, long ldx, long sX, long ldtn,
+                     long sTn, void* stream);
+int xk_herm_cholqr_c128(double* W, double* MW, double* Rinv, int* info, int B, int q, int N, long ldw, long sW,
+                        long ldmw, long sMW, double shift_rel, void* stream);
+int xk_herm_cholqr_c64(float* W, float* MW, float* Rinv, int* info, int B, int q, int N, long ldw, long sW,
+                       long ldmw, long sMW, double shift_rel, void* stream);
+
 /* ---- fused BLAS-1 of the quasi-Newton (Broyden) driver -------------------------------------------------
  * The reference's _nonlin_solver / LowRankMatrix (xitorch/_impls/optimize/root/rootsolver.py:96-143,
  * _jacobian.py:99-119,172-189) run torch.dot / .norm() / axpy chains on one flat length-L vector with a host sync

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("XITORCH_AMD_LIB") or os.path.join(_HERE, "csrc", "lib
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "xitorch_amd.h")
 
 _lib = None
-ABI_VERSION = 1          # xk_abi_version() of the library this package was written against
+ABI_VERSION = 2          # xk_abi_version() of the library this package was written against
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -135,6 +135,12 @@ def _declare(L):
         sigs["xk_kry_resid_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, P])
         sigs["xk_cg_update_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
         sigs["xk_cg_p_" + sfx] = (I, [P] * 4 + [I, I, Lg, I, D, P])
+    sigs["xk_herm_eigh_lds_bytes"] = (Lg, [I, I, I])
+    sigs["xk_herm_eigh_workspace_elems"] = (Lg, [I, I, I])
+    for sfx in ("c128", "c64"):
+        sigs["xk_herm_eigh_" + sfx] = (I, [P, P, P, P, P, Lg, I, I, I, I, Lg, Lg, P])
+        sigs["xk_herm_ritz_" + sfx] = (I, [P] * 8 + [I, I, I, I] + [Lg] * 14 + [P])
+        sigs["xk_herm_cholqr_" + sfx] = (I, [P, P, P, P, I, I, I, Lg, Lg, Lg, Lg, D, P])
     sigs["xk_comm_available"] = (I, [])
     sigs["xk_comm_unique_id"] = (I, [P])
     sigs["xk_comm_init_rank"] = (I, [P, I, I, I, P])

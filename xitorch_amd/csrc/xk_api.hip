@@ -1,7 +1,7 @@
 // xitorch_amd :: ABI bookkeeping
 #include "xk_common.h"
 
-extern "C" int xk_abi_version(void) { return 1; }
+extern "C" int xk_abi_version(void) { return 2; }
 
 // ---------------------------------------------------------------------------------------------
 // Stream restricted to a subset of the compute units.

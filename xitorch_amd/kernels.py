@@ -557,6 +557,98 @@ def dense_outer_complex(U, W):
     return torch.view_as_complex(G.view(B, M, N, 2))
 
 
+# --------------------------------------------------------------------------- Hermitian Davidson chain (complex)
+HERM_EIGH_MAX_K = 128        # order of the Rayleigh-Ritz matrix xk_herm_eigh serves (both complex types)
+HERM_EIGH_MAX_P = 16         # wanted pairs per call
+HERM_CHOLQR_MAX_Q = 32       # block width of xk_herm_cholqr
+
+
+def _real_view(t):
+    """the interleaved (re, im) storage of a complex tensor as a real tensor (zero-copy)"""
+    if t.is_conj():
+        raise _capi.NativeLibraryError("Hermitian Davidson kernels take resolved tensors, got a conjugate view")
+    return torch.view_as_real(t)
+
+
+def _ld(t):
+    """pitch between the vectors of a (B, q, N) panel (a one-vector panel may carry any stride there)"""
+    return t.stride(1) if t.shape[1] > 1 else t.shape[2]
+
+
+def herm_eigh_ok(k, p):
+    return 1 <= p <= min(k, HERM_EIGH_MAX_P) and k <= HERM_EIGH_MAX_K
+
+
+def herm_eigh(T, k, p, uppest=False):
+    """Lowest / uppermost `p` eigenpairs of the Hermitian (B, k, k) complex matrices T[:, :k, :k] (lower triangle
+    read): lam (B, p) real ascending, Y (B, p, k) complex with Y[b, c] the c-th eigenvector, flags (B,) int32
+    (nonzero: the self-check failed, redo that member on the library).  The complex counterpart of `small_eigh(...,
+    method="tri")`; replaces torch.linalg.eigh + _take_eigpairs (symeig.py:174-175) for complex bases."""
+    require_device(T, "projected matrix")
+    if not herm_eigh_ok(k, p):
+        raise _capi.NativeLibraryError("herm_eigh serves k <= %d, p <= min(k, %d); got k = %d, p = %d"
+                                       % (HERM_EIGH_MAX_K, HERM_EIGH_MAX_P, k, p))
+    B = T.shape[0]
+    if T.dim() != 3 or T.stride(2) != 1 or T.shape[1] < k or T.shape[2] < k:
+        raise _capi.NativeLibraryError("T must be (B, >=k, >=k) with unit stride along its last dim")
+    rdt = torch.float64 if T.dtype == torch.complex128 else torch.float32
+    lam = torch.empty((B, p), dtype=rdt, device=T.device)
+    Y = torch.empty((B, p, k), dtype=T.dtype, device=T.device)
+    info = torch.empty((B,), dtype=torch.int32, device=T.device)
+    nws = fn("xk_herm_eigh_workspace_elems")(B, k, p)
+    ws = _workspace(max(nws, 1), rdt, T.device)
+    rc = fn("xk_herm_eigh_" + suffix(T.dtype))(ptr(_real_view(T)), ptr(lam), ptr(_real_view(Y)), ptr(info), ptr(ws),
+                                                nws, B, k, p, 1 if uppest else 0, T.stride(1), T.stride(0),
+                                                stream_ptr())
+    check(rc, "xk_herm_eigh")
+    return lam, Y, info
+
+
+def herm_ritz(V, AV, Y, lam, X, Tn, status, k, p, MV=None):
+    """Fused Ritz step of the complex driver (xk_herm_ritz): X[:, :p] = Y^T V[:, :k], Tn[:, :p] = -(Y^T AV - lam Y^T MV),
+    status (B + 1 float64) = {max over the batch, max per member} of |R| (complex modulus).  V, AV, MV: (B, >=k, ld)
+    panels; Y (B, >=k, >=p) complex (any strides), lam (B, >=p) real, unit stride along p (symeig.py:178-188)."""
+    require_device(V, "basis")
+    B, N = V.shape[0], V.shape[2]
+    if Y.dim() != 3 or Y.shape[0] != B or Y.shape[1] < k or Y.shape[2] < p or lam.shape[0] != B or lam.shape[-1] < p:
+        raise _capi.NativeLibraryError("herm_ritz: Y must be (B, >=k, >=p) and lam (B, >=p)")
+    if lam.stride(-1) != 1 and p > 1:
+        raise _capi.NativeLibraryError("lam must have unit stride along its last dim")
+    for t, rows in ((V, k), (AV, k), (MV, k), (X, p), (Tn, p)):
+        if t is not None and (t.dim() != 3 or t.shape[0] != B or t.shape[1] < rows or t.shape[2] != N or
+                              t.stride(2) != 1 or t.dtype != V.dtype):
+            raise _capi.NativeLibraryError("herm_ritz: panels must be (B, rows, N) of one dtype, unit stride along N")
+    if status.numel() < B + 1 or status.dtype != torch.float64:
+        raise _capi.NativeLibraryError("herm_ritz: status needs B + 1 float64 elements")
+    M_ = MV if MV is not None else V
+    rc = fn("xk_herm_ritz_" + suffix(V.dtype))(
+        ptr(_real_view(V)), ptr(_real_view(AV)), ptr(_real_view(MV)) if MV is not None else None, ptr(_real_view(Y)),
+        ptr(lam), ptr(_real_view(X)), ptr(_real_view(Tn)), ptr(status), B, k, N, p, _ld(V), V.stride(0),
+        _ld(AV), AV.stride(0), _ld(M_), M_.stride(0), Y.stride(0), Y.stride(1), Y.stride(2), lam.stride(0),
+        _ld(X), X.stride(0), _ld(Tn), Tn.stride(0), stream_ptr())
+    check(rc, "xk_herm_ritz")
+
+
+def herm_cholqr(W, info, MW=None, shift_rel=0.0):
+    """CholeskyQR of the complex block W (B, q, N) in place, in the M-inner product when MW = M W is given (then MW is
+    transformed alike): G = W^H MW, G + shift_rel trace(G) I = R^H R, W <- W R^-1.  info (B,) int32, sticky: index + 1
+    of the first non-positive pivot.  tallqr of the new block (_utils/tensor.py:8-19)."""
+    require_device(W, "block")
+    B, q, N = W.shape
+    if q > HERM_CHOLQR_MAX_Q:
+        raise _capi.NativeLibraryError("herm_cholqr serves blocks of up to %d vectors, got %d" % (HERM_CHOLQR_MAX_Q, q))
+    for t in (W, MW):
+        if t is not None and (t.shape != W.shape or t.stride(2) != 1 or t.dtype != W.dtype):
+            raise _capi.NativeLibraryError("herm_cholqr: blocks must be (B, q, N) of one dtype, unit stride along N")
+    Rinv = torch.empty((B, q, q), dtype=W.dtype, device=W.device)
+    rc = fn("xk_herm_cholqr_" + suffix(W.dtype))(
+        ptr(_real_view(W)), ptr(_real_view(MW)) if MW is not None else None, ptr(_real_view(Rinv)), ptr(info), B, q, N,
+        _ld(W), W.stride(0), _ld(MW) if MW is not None else 0, MW.stride(0) if MW is not None else 0,
+        float(shift_rel), stream_ptr())
+    check(rc, "xk_herm_cholqr")
+    return Rinv
+
+
 # --------------------------------------------------------------------------- measurement utility
 def stream_read(t):
     """Enqueue one read-only pass over the storage of the contiguous HIP tensor `t` (rows = its last dimension; the

@@ -956,10 +956,17 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
                                  process_group=process_group, trace=trace, precond=precond, restart=restart)
     if device.type != "cuda":
         raise NativeLibraryError("xitorch_amd davidson runs on a HIP device only (operator is on %s)" % device)
+    if dtype in (torch.complex128, torch.complex64):
+        # complex Hermitian operators: the same iteration on the complex kernels (native_eig_herm.py); the reference's
+        # davidson is real-only (unconjugated transposes, symeig.py:163)
+        from xitorch_amd.linalg import native_eig_herm
+        return native_eig_herm.davidson(A, neig, mode, M, max_niter=max_niter, nguess=nguess, v_init=v_init,
+                                        max_addition=max_addition, min_eps=min_eps, verbose=verbose, V0=V0,
+                                        process_group=process_group, trace=trace, rng_device=rng_device,
+                                        precond=precond, restart=restart)
     if dtype not in (torch.float64, torch.float32):
-        raise NativeLibraryError("xitorch_amd davidson supports float64/float32 operators, got %s (the reference's "
-                                 "davidson is real-only as well: unconjugated transposes, symeig.py:163; complex "
-                                 "Hermitian operators go through method='exacteig')" % dtype)
+        raise NativeLibraryError("xitorch_amd davidson supports float64/float32 and complex128/complex64 operators, "
+                                 "got %s" % dtype)
     B = 1
     for d in bdims:
         B *= d
