@@ -180,7 +180,10 @@ __global__ __launch_bounds__(256) void ritz_residual_kernel(
       for (int v = 0; v < VN; ++v) {
         const T r = ax[c][v] - l * xx[c][v];
         t[v] = -r;
-        const T ar = r < T(0) ? -r : r;
+        // NaN never compares greater, so it would be dropped by this max and by wave_max: report it as +inf here,
+        // where it is still visible, so the host loop cannot "converge" on it (finite values are unchanged)
+        T ar = r < T(0) ? -r : r;
+        ar = ar != ar ? T(INFINITY) : ar;
         local_max = ar > local_max ? ar : local_max;
       }
       *reinterpret_cast<VT*>(X + (long)b * sX + (long)c * ldx + j) = xx[c];
@@ -195,8 +198,7 @@ __global__ __launch_bounds__(256) void ritz_residual_kernel(
     m = red[1] > m ? red[1] : m;
     m = red[2] > m ? red[2] : m;
     m = red[3] > m ? red[3] : m;
-    // NaN never compares greater: make it visible as +inf so the host loop cannot "converge" on it
-    if (m != m) m = T(INFINITY);
+    // (no NaN reaches this point: each lane mapped it to +inf above, and +inf orders as the largest bit pattern)
     atomic_max_nonneg(rmax + b, m);
   }
 }
