@@ -253,6 +253,32 @@ int xk_banded_mm_f64(const double* band, const double* X, double* Y, int B, int 
 int xk_banded_mm_f32(const float* band, const float* X, float* Y, int B, int N, int hb, int C,
                      long sBand, long ldx, long sX, long ldy, long sY, int trans, void* stream);
 
+/* ---- CSR sparse operator (one pattern shared by the batch) ---------------------------------------
+ * xk_csr_mm:    Y[b,c,i] = sum_{ptr[i] <= k < ptr[i+1]} val[b*sV + (perm ? perm[k] : k)] X[b,c,idx[k]]
+ *   for the Mout rows listed in rows[0 .. Mout): rows is a permutation of 0 .. Mout-1 grouped into 4 bins by row
+ *   length, bin q = rows[bin_off[q] .. bin_off[q+1]) (bin_off: HOST array of 5 ints, bin_off[4] = Mout).  Bins 0-2
+ *   are served by 1 / 8 / 64 lanes per row; the rows of bin 3 (nlong = bin_off[4] - bin_off[3]) are cut into
+ *   segments of xk_csr_seg_len() entries: long row q owns segments seg_off[q] .. seg_off[q+1] (seg_off: nlong+1
+ *   device ints), seg_q[s] = the long row of segment s (nseg device ints), and ws (device, >= B * min(C, 8) * nseg
+ *   elements) holds the segment sums, added per row in segment order.  The transposed operator is the same call on
+ *   the CSC view (ptr = column pointers, idx = row indices, perm = CSR position of each CSC entry).  Fixed summation
+ *   order, no atomics.  sV = 0 broadcasts one set of values over the batch.  X (B, C, ldx >= Nin),
+ *   Y (B, C, ldy >= Mout) panel-major; only the Mout leading entries of each Y vector are written.
+ * xk_csr_sddmm: G[b,k] = sum_c U[b,c,row_of[k]] W[b,c,col[k]]  (the values gradient; transposed apply: swap U and
+ *   W; batch dims the values lack are folded into the columns by the caller).  U (B, C, ldu >= M),
+ *   W (B, C, ldw >= N).  Indices are int32 and must be in range (checked once by the operator). */
+int xk_csr_seg_len(void);
+int xk_csr_mm_f64(const int* ptr, const int* idx, const int* perm, const double* val, long sV, const int* rows,
+                  const int* bin_off, const int* seg_q, const int* seg_off, int nseg, double* ws, const double* X,
+                  double* Y, int B, int Mout, int Nin, int C, long ldx, long sX, long ldy, long sY, void* stream);
+int xk_csr_mm_f32(const int* ptr, const int* idx, const int* perm, const float* val, long sV, const int* rows,
+                  const int* bin_off, const int* seg_q, const int* seg_off, int nseg, float* ws, const float* X,
+                  float* Y, int B, int Mout, int Nin, int C, long ldx, long sX, long ldy, long sY, void* stream);
+int xk_csr_sddmm_f64(const int* row_of, const int* col, const double* U, const double* W, double* G, int nnz, int B,
+                     int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
+int xk_csr_sddmm_f32(const int* row_of, const int* col, const float* U, const float* W, float* G, int nnz, int B,
+                     int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
+
 /* ---- operator gradients of the implicit backward passes (streaming writes) -----------------------
  * The backward of solve / symeig / rootfinder ends with a VJP through the operator apply
  * (`loss = -A.mm(x)`; `autograd.grad(loss, params, v)`: xitorch/linalg/solve.py:188-195,

@@ -94,6 +94,7 @@ def _declare(L):
     for sfx in ("f64", "f32"):
         sigs["xk_small_eigh_big_" + sfx] = (I, [P, P, P, P, Lg, P, I, I, I, I, Lg, Lg, I, I, I, P])
     sigs["xk_kry_max_partials"] = (I, [])
+    sigs["xk_csr_seg_len"] = (I, [])
     sigs["xk_dense_symm_workspace_elems"] = (Lg, [I, I, I, I])
     sigs["xk_dense_symm_wide_workspace_elems"] = (Lg, [I, I])
     sigs["xk_dense_symm_wide_f32"] = (I, [P, P, P, P, Lg, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
@@ -123,6 +124,8 @@ def _declare(L):
         sigs["xk_kry_status_" + sfx] = (I, [P] * 4 + [I, I, P])
         sigs["xk_banded_grad_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, I, P])
         sigs["xk_dense_outer_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
+        sigs["xk_csr_mm_" + sfx] = (I, [P, P, P, P, Lg, P, P, P, P, I, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, P])
+        sigs["xk_csr_sddmm_" + sfx] = (I, [P, P, P, P, P, I, I, I, I, I, Lg, Lg, Lg, Lg, Lg, P])
     for sfx in ("f64", "f32"):
         sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
         sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])

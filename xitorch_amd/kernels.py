@@ -416,6 +416,64 @@ def banded_grad(U, W, nd, out=None, accumulate=False):
     return out
 
 
+# --------------------------------------------------------------------------- CSR sparse operator
+def csr_mm(pat, values, X, out=None, trans=False):
+    """Y[b,c,:] = A_b X[b,c,:] (trans: A_b^T X[b,c,:]) for a CSR operator whose pattern `pat` (linop._CsrPattern:
+    int32 device index arrays and the row bins) is shared by the batch.  values (B or 1, nnz) contiguous rows,
+    X panel-major (B, C, N) (trans: (B, C, M)); returns Y (B, C, M) (trans: (B, C, N))."""
+    require_device(values, "values")
+    require_device(X, "panel")
+    if values.dtype != X.dtype:
+        raise _capi.NativeLibraryError("dtype mismatch %s vs %s" % (values.dtype, X.dtype))
+    B, C, nin = X.shape
+    v = pat.csc() if trans else pat.csr()
+    if nin != v.n_in:
+        raise _capi.NativeLibraryError("panel length %d != operator dim %d" % (nin, v.n_in))
+    if values.dim() != 2 or values.shape[-1] != pat.nnz or values.shape[0] not in (1, B) or \
+            (pat.nnz > 1 and values.stride(-1) != 1):
+        raise _capi.NativeLibraryError("values must be (1 or %d, %d) with unit stride, got %s"
+                                       % (B, pat.nnz, tuple(values.shape)))
+    if values.device != X.device or v.ptr.device != X.device:
+        raise _capi.NativeLibraryError("values, pattern and panel must share one device")
+    sV = values.stride(0) if values.shape[0] != 1 else 0
+    ldx, sX = _panel_strides(X)
+    if out is None:
+        out = torch.empty((B, C, v.n_out), dtype=X.dtype, device=X.device)
+    if out.shape != (B, C, v.n_out):
+        raise _capi.NativeLibraryError("output must be (%d, %d, %d), got %s" % (B, C, v.n_out, tuple(out.shape)))
+    ldy, sY = _panel_strides(out)
+    ws = v.scratch(B * min(C, 8) * v.nseg, X.dtype) if v.nseg else None
+    rc = fn("xk_csr_mm_" + suffix(X.dtype))(ptr(v.ptr), ptr(v.idx), ptr(v.perm), ptr(values), sV, ptr(v.rows),
+                                             v.bin_off, ptr(v.seg_q), ptr(v.seg_off), v.nseg, ptr(ws), ptr(X),
+                                             ptr(out), B, v.n_out, nin, C, ldx if C > 1 else max(ldx, nin), sX,
+                                             ldy if C > 1 else max(ldy, v.n_out), sY, stream_ptr())
+    check(rc, "xk_csr_mm")
+    return out
+
+
+def csr_sddmm(pat, U, W, out=None):
+    """G[b,k] = sum_c U[b,c,row_k] W[b,c,col_k]  — the values gradient of the CSR apply (y = A x: U = grad y, W = x;
+    y = A^T x: U = x, W = grad y).  U (B, C, M), W (B, C, N) panel-major; returns G (B, nnz).  Batch dims the values
+    do not have are folded into C by the caller, so the kernel sums them in its fixed order."""
+    require_device(U, "panel")
+    require_device(W, "panel")
+    B, C, M = U.shape
+    if W.dim() != 3 or W.shape[:2] != U.shape[:2] or U.dtype != W.dtype or M != pat.M or W.shape[2] != pat.N:
+        raise _capi.NativeLibraryError("csr_sddmm: panels (B, C, %d) / (B, C, %d) expected, got %s / %s"
+                                       % (pat.M, pat.N, tuple(U.shape), tuple(W.shape)))
+    ldu, sU = _panel_strides(U)
+    ldw, sW = _panel_strides(W)
+    if out is None:
+        out = torch.empty((B, pat.nnz), dtype=U.dtype, device=U.device)
+    if out.shape != (B, pat.nnz) or (pat.nnz > 1 and out.stride(-1) != 1):
+        raise _capi.NativeLibraryError("csr_sddmm: output must be (%d, %d) with unit stride" % (B, pat.nnz))
+    rc = fn("xk_csr_sddmm_" + suffix(U.dtype))(ptr(pat.row_of), ptr(pat.col), ptr(U), ptr(W), ptr(out), pat.nnz, B,
+                                                M, pat.N, C, ldu if C > 1 else max(ldu, M), sU,
+                                                ldw if C > 1 else max(ldw, pat.N), sW, out.stride(0), stream_ptr())
+    check(rc, "xk_csr_sddmm")
+    return out
+
+
 def dense_outer(U, W, out=None, accumulate=False):
     """G[b,i,j] (+)= sum_c U[b,c,i] * W[b,c,j]  — the dense-operator gradient (outer product of two panels).
     U (B, C, M), W (B, C, N) panel-major; returns (B, M, N) row-major."""

@@ -7,6 +7,7 @@ out[b, c, :N] = A_b x[b, c, :N] (or A_b^H) without any layout copies for the nat
 
   MatrixLinearOperator  -> xk_dense_mm   (K1; column-oriented variant when the matrix is symmetric)
   BandedLinearOperator  -> xk_banded_mm
+  SparseLinearOperator  -> xk_csr_mm     (fp32 / fp64 values; the transpose on the pattern's CSC view)
   anything else         -> the operator's own .mm/.rmm on the (.., N, p) strided view
 """
 import torch
@@ -36,13 +37,13 @@ def from_panel(P, bdims, N):
 
 class PanelOperator:
     def __init__(self, A, bdims, Bt, N):
-        from xitorch_amd.linop import MatrixLinearOperator, BandedLinearOperator
+        from xitorch_amd.linop import MatrixLinearOperator, BandedLinearOperator, SparseLinearOperator
         self.A, self.bdims, self.Bt, self.N = A, list(bdims), Bt, N
         self.kind = "generic"
         self.symm = False
         self.symm_narrow = False
         self.napply = 0
-        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded)
+        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded / csr)
         self.events = None          # when a list: (start, end, p) HIP events around every native launch
         self.hermitian = bool(getattr(A, "is_hermitian", False))
         nA = 1
@@ -80,6 +81,12 @@ class PanelOperator:
                 and A.band.is_contiguous():
             self.kind = "banded"
             self.band = A.band.reshape(nA, *A.band.shape[-2:])
+        elif isinstance(A, SparseLinearOperator) and native_t(A.values) and (nA == Bt or nA == 1):
+            self.kind = "csr"
+            self.pat = A._pattern
+            self.vals = A.values.reshape(-1, A.nnz)
+            if A.nnz > 1 and self.vals.stride(-1) != 1:
+                self.vals = self.vals.contiguous()
 
     def diagonal(self):
         """diag(A) as a contiguous (nA, N) array (native operators only)."""
@@ -89,6 +96,11 @@ class PanelOperator:
         if self.kind == "banded":
             hb = (self.band.shape[-2] - 1) // 2
             return self.band[:, hb, :].contiguous()
+        if self.kind == "csr":
+            # once per solve: the stored entries on the diagonal, duplicates summed
+            on = self.pat.row_of == self.pat.col
+            d = torch.zeros((self.vals.shape[0], self.N), dtype=self.vals.dtype, device=self.vals.device)
+            return d.index_add(1, self.pat.col[on].to(torch.int64), self.vals[:, on]).contiguous()
         raise K._capi.NativeLibraryError("the diagonal of a generic LinearOperator is not available: pass it "
                                          "explicitly (precond=<tensor (*batch, N)>) or use a LinearOperator")
 
@@ -177,6 +189,9 @@ class PanelOperator:
             else:
                 self.last_kernel = "K1wr" if wide else "K1"
             K.dense_mm(self.mat, Xn, out=out[:, :, :N], trans=t)
+        elif self.kind == "csr":
+            self.last_kernel = "csr"
+            K.csr_mm(self.pat, self.vals, X[:, :, :N], out=out[:, :, :N], trans=trans)
         else:
             self.last_kernel = "banded"
             K.banded_mm(self.band, X[:, :, :N], out=out[:, :, :N], trans=trans)

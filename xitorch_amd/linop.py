@@ -24,7 +24,8 @@ from xitorch_amd.debug import is_debug_enabled
 from xitorch_amd._util import bcast_shape
 from xitorch_amd import kernels as _k
 
-__all__ = ["LinearOperator", "MatrixLinearOperator", "BandedLinearOperator", "RowShardedMatrixLinearOperator"]
+__all__ = ["LinearOperator", "MatrixLinearOperator", "BandedLinearOperator", "SparseLinearOperator",
+           "RowShardedMatrixLinearOperator"]
 
 
 class LinearOperator(EditableModule):
@@ -874,6 +875,289 @@ class BandedLinearOperator(LinearOperator):
 
     def _getparamnames(self, prefix=""):
         return [prefix + "band"]
+
+
+# ------------------------------------------------------------------------ native CSR sparse operator
+_CSR_BIN_EDGES = (4, 32, 1024)      # row-length bin edges of xk_csr_mm (1 / 8 / 64 / 256 lanes per row)
+
+
+class _CsrView:
+    """One orientation of a pattern as xk_csr_mm reads it: pointers, indices, the value permutation (None in the
+    CSR orientation), the output rows grouped by length bin (bin_off: host int[5]) and the segments of the long rows
+    (seg_q: long row of each segment, seg_off: first segment of each long row), plus the segment-sum scratch."""
+
+    def __init__(self, ptr, idx, perm, n_out, n_in):
+        import ctypes
+        self.ptr, self.idx, self.perm, self.n_out, self.n_in = ptr, idx, perm, n_out, n_in
+        lens = (ptr[1:] - ptr[:-1]).to(torch.int64)
+        edges = torch.tensor(_CSR_BIN_EDGES, dtype=torch.int64, device=ptr.device)
+        binid = torch.bucketize(lens, edges, right=False)             # len <= 4 -> 0, <= 32 -> 1, <= 1024 -> 2, else 3
+        order = torch.sort(binid, stable=True).indices                  # rows ascending inside each bin
+        self.rows = order.to(torch.int32).contiguous()
+        counts = torch.bincount(binid, minlength=4).tolist()
+        offs = [0]
+        for c in counts:
+            offs.append(offs[-1] + int(c))
+        self.bin_counts = counts
+        self.bin_off = (ctypes.c_int * 5)(*offs)
+        self.seg_q = self.seg_off = None
+        self.nseg = 0
+        self._ws = None
+        if counts[3]:
+            seg = int(_k.fn("xk_csr_seg_len")())
+            nsq = (lens[order[offs[3]:]] + seg - 1) // seg                 # segments of each long row
+            so = torch.zeros(counts[3] + 1, dtype=torch.int64, device=ptr.device)
+            so[1:] = torch.cumsum(nsq, 0)
+            self.nseg = int(so[-1])
+            self.seg_off = so.to(torch.int32)
+            self.seg_q = torch.repeat_interleave(torch.arange(counts[3], dtype=torch.int32, device=ptr.device), nsq,
+                                                 output_size=self.nseg)
+
+    def scratch(self, n, dtype):
+        if self._ws is None or self._ws.numel() < n or self._ws.dtype != dtype:
+            self._ws = torch.empty(n, dtype=dtype, device=self.ptr.device)
+        return self._ws
+
+
+class _CsrPattern:
+    """Sparsity structure shared by the batch: int32 CSR arrays, the row of every entry, and — built on first
+    use — the row bins of the native apply and the CSC view (stable argsort of (col, row)) of the transposed one."""
+
+    def __init__(self, crow, col, M, N):
+        self.crow, self.col, self.M, self.N = crow, col, M, N
+        self.nnz = col.numel()
+        self.row_of = torch.repeat_interleave(torch.arange(M, dtype=torch.int32, device=crow.device),
+                                              (crow[1:] - crow[:-1]).to(torch.int64), output_size=self.nnz)
+        self._csr = self._csc = None
+        self._ccol = self._row_idx = self._perm = None
+
+    def csr(self):
+        if self._csr is None:
+            self._csr = _CsrView(self.crow, self.col, None, self.M, self.N)
+        return self._csr
+
+    def transposed(self):
+        """(ccol_ptr (N+1,), row_idx (nnz,), perm (nnz,)) int32: the CSC view; perm[k] = CSR position of entry k."""
+        if self._perm is None:
+            key = self.col.to(torch.int64) * max(self.M, 1) + self.row_of.to(torch.int64)
+            perm = torch.sort(key, stable=True).indices
+            cnt = torch.bincount(self.col.to(torch.int64), minlength=self.N)
+            ccol = torch.zeros(self.N + 1, dtype=torch.int64, device=self.col.device)
+            ccol[1:] = torch.cumsum(cnt, 0)
+            self._ccol = ccol.to(torch.int32)
+            self._row_idx = self.row_of[perm].contiguous()
+            self._perm = perm.to(torch.int32).contiguous()
+        return self._ccol, self._row_idx, self._perm
+
+    def csc(self):
+        if self._csc is None:
+            ccol, row_idx, perm = self.transposed()
+            self._csc = _CsrView(ccol, row_idx, perm, self.N, self.M)
+        return self._csc
+
+
+def csr_apply_torch(crow, col, values, x, M, N, trans=False, row_of=None):
+    """Reference semantics of the CSR apply in plain torch (host tensors, complex values): y = A x (trans: A^H x),
+    A[..., i, col[k]] += values[..., k] for crow[i] <= k < crow[i+1] — duplicates add up.  x (*Bx, N, r) (trans:
+    (*Bx, M, r)); values (*Bv, nnz)."""
+    if row_of is None:
+        row_of = torch.repeat_interleave(torch.arange(M, device=crow.device), (crow[1:] - crow[:-1]).to(torch.int64),
+                                         output_size=col.numel())
+    row_of, col = row_of.to(torch.int64), col.to(torch.int64)
+    src, dst, nout = (row_of, col, N) if trans else (col, row_of, M)
+    v = values.conj() if trans else values
+    dt = torch.promote_types(values.dtype, x.dtype)
+    terms = v.unsqueeze(-1).to(dt) * x.index_select(-2, src).to(dt)          # (*FB, nnz, r)
+    y = torch.zeros((*terms.shape[:-2], nout, x.shape[-1]), dtype=dt, device=x.device)
+    return y.index_add(-2, dst, terms)
+
+
+class _CsrMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, x, pat, trans):
+        ctx.save_for_backward(values, x)
+        ctx.pat, ctx.trans = pat, trans
+        return _csr_native(pat, values, x, trans)
+
+    @staticmethod
+    def backward(ctx, gy):
+        values, x = ctx.saved_tensors
+        pat = ctx.pat
+        gval = gx = None
+        if ctx.needs_input_grad[1] and _grad_wanted(x):
+            gx = _sum_to_shape(_CsrMM.apply(values, gy, pat, not ctx.trans), x.shape)
+        if ctx.needs_input_grad[0] and _grad_wanted(values):
+            # d/dval[k] = sum_c gy[row_k, c] x[col_k, c]  (trans: x[row_k, c] gy[col_k, c]) — xk_csr_sddmm
+            gval = _CsrGrad.apply(x, gy, pat, tuple(values.shape)) if ctx.trans else \
+                _CsrGrad.apply(gy, x, pat, tuple(values.shape))
+        return gval, gx, None, None
+
+
+class _CsrGrad(torch.autograd.Function):
+    """G[..., k] = sum_c u[..., row_k, c] w[..., col_k, c] reduced to the values' shape (xk_csr_sddmm): the gradient
+    of the CSR apply w.r.t. the stored values.  Batch dims the values do not have are folded into the columns, so
+    the kernel sums them in a fixed order.  Bilinear: its backward is two CSR applies with G as the values."""
+
+    @staticmethod
+    def forward(ctx, u, w, pat, vshape):
+        ctx.save_for_backward(u, w)
+        ctx.pat = pat
+        nb, FB, keep, fold = _batch_plan(vshape[:-1], u.shape[:-2], w.shape[:-2])
+        up, wp = _to_panel(u, nb, FB, keep, fold), _to_panel(w, nb, FB, keep, fold)
+        g = _k.csr_sddmm(pat, up, wp)                                      # (nkeep, nnz)
+        return g.reshape(vshape)
+
+    @staticmethod
+    def backward(ctx, gg):
+        u, w = ctx.saved_tensors
+        pat = ctx.pat
+        gu = gw = None
+        if ctx.needs_input_grad[0]:
+            gu = _sum_to_shape(_CsrMM.apply(gg, w, pat, False), u.shape)
+        if ctx.needs_input_grad[1]:
+            gw = _sum_to_shape(_CsrMM.apply(gg, u, pat, True), w.shape)
+        return gu, gw, None, None
+
+
+def _csr_native(pat, values, x, trans):
+    nout = pat.N if trans else pat.M
+    r = x.shape[-1]
+    nb, FB, keep, fold = _batch_plan(list(values.shape[:-1]), list(x.shape[:-2]))
+    xp = _to_panel(x, nb, FB, keep, fold)                                  # (nkeep, fold * r, nin)
+    valf = values.reshape(-1, pat.nnz)
+    if pat.nnz > 1 and valf.stride(-1) != 1:
+        valf = valf.contiguous()
+    y = _k.csr_mm(pat, valf, xp, trans=trans)
+    y = y.reshape(*[FB[d] for d in keep], *[FB[d] for d in fold], r, nout)
+    inv = [0] * (nb + 2)
+    for pos, d in enumerate(keep + fold + [nb + 1, nb]):
+        inv[d] = pos
+    return y.permute(*inv)
+
+
+class SparseLinearOperator(LinearOperator):
+    """Sparse operator in CSR storage with one pattern shared by the batch: ``crow_indices (M+1,)``,
+    ``col_indices (nnz,)`` (int32 or int64, kept as int32) and ``values (*B, nnz)`` or ``(nnz,)`` (broadcast over
+    the batch); ``shape`` is ``(M, N)`` or ``(*B, M, N)``.  Duplicate (row, col) entries add up, columns need not be
+    sorted, empty rows and nnz = 0 are legal.  The structure is validated once, here.
+
+    fp32 / fp64 values on a HIP device are applied by the xk_csr_mm HIP kernel (its transpose on a CSC view built
+    on first use) and differentiated w.r.t. the values by xk_csr_sddmm; host tensors and complex values use the
+    torch expression ``csr_apply_torch``.  Only ``values`` is a parameter (``_getparamnames``): the indices are
+    structure, so ``uselinopparams`` and the implicit backward swap the values alone."""
+
+    def __init__(self, crow_indices, col_indices, values, shape, is_hermitian=False):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) < 2:
+            raise RuntimeError("SparseLinearOperator: shape must be (*B, M, N), got %s" % (shape,))
+        M, N = shape[-2:]
+        bshape = shape[:-2] if len(shape) > 2 else tuple(values.shape[:-1])
+        crow, col = crow_indices, col_indices
+        for name, t in (("crow_indices", crow), ("col_indices", col)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+                raise RuntimeError("SparseLinearOperator: %s must be a 1-D int32 / int64 tensor" % name)
+        if not isinstance(values, torch.Tensor) or values.dim() < 1:
+            raise RuntimeError("SparseLinearOperator: values must be a tensor (*B, nnz) or (nnz,)")
+        nnz = col.numel()
+        if M < 0 or N < 0 or M >= 2 ** 31 or N >= 2 ** 31:
+            raise RuntimeError("SparseLinearOperator: dimensions (%d, %d) out of the int32 range" % (M, N))
+        if nnz >= 2 ** 31:
+            raise RuntimeError("SparseLinearOperator: nnz = %d does not fit int32 indices (< 2^31)" % nnz)
+        if crow.numel() != M + 1:
+            raise RuntimeError("SparseLinearOperator: crow_indices must have M+1 = %d entries, got %d"
+                               % (M + 1, crow.numel()))
+        if values.shape[-1] != nnz:
+            raise RuntimeError("SparseLinearOperator: values have %d entries per member, col_indices %d"
+                               % (values.shape[-1], nnz))
+        if tuple(values.shape[:-1]) not in ((), bshape):
+            raise RuntimeError("SparseLinearOperator: values batch %s does not match the operator batch %s"
+                               % (tuple(values.shape[:-1]), bshape))
+        if crow.device != values.device or col.device != values.device:
+            raise RuntimeError("SparseLinearOperator: indices and values must live on one device (%s, %s, %s)"
+                               % (crow.device, col.device, values.device))
+        c64 = crow.to(torch.int64)
+        if int(c64[0]) != 0:
+            raise RuntimeError("SparseLinearOperator: crow_indices[0] must be 0, got %d" % int(c64[0]))
+        if M > 0 and bool((c64[1:] < c64[:-1]).any()):
+            raise RuntimeError("SparseLinearOperator: crow_indices must be non-decreasing")
+        if int(c64[-1]) != nnz:
+            raise RuntimeError("SparseLinearOperator: crow_indices[-1] = %d must equal nnz = %d" % (int(c64[-1]), nnz))
+        if nnz > 0:
+            lo, hi = int(col.min()), int(col.max())
+            if lo < 0 or hi >= N:
+                raise RuntimeError("SparseLinearOperator: column index out of range [0, %d): found %d"
+                                   % (N, lo if lo < 0 else hi))
+        super().__init__(shape=(*bshape, M, N), is_hermitian=is_hermitian, dtype=values.dtype, device=values.device,
+                         _suppress_hermit_warning=True)
+        self.crow = crow.to(torch.int32).contiguous()
+        self.col = col.to(torch.int32).contiguous()
+        self.values = values
+        self.nnz = nnz
+        self._pattern = _CsrPattern(self.crow, self.col, M, N)
+        if values.is_cuda:
+            self._pattern.csr()               # bin the rows once, at construction
+
+    @classmethod
+    def from_torch(cls, t, is_hermitian=False):
+        """From a 2-D torch sparse CSR or COO tensor, or a batched CSR tensor whose members share one pattern."""
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("SparseLinearOperator.from_torch: expected a torch sparse tensor, got %s" % type(t))
+        if t.layout == torch.sparse_coo:
+            if t.dim() != 2 or t.dense_dim() != 0:
+                raise RuntimeError("SparseLinearOperator.from_torch: only a 2-D COO tensor is accepted, got %s"
+                                   % (tuple(t.shape),))
+            M, N = t.shape
+            idx = t._indices().to(torch.int64)
+            vals = t._values()
+            # stable sort by row: entries keep their order inside a row, duplicates are summed by the apply
+            order = torch.sort(idx[0], stable=True).indices
+            rows, cols, vals = idx[0][order], idx[1][order], vals[order]
+            crow = torch.zeros(M + 1, dtype=torch.int64, device=t.device)
+            crow[1:] = torch.cumsum(torch.bincount(rows, minlength=M), 0)
+            return cls(crow, cols, vals, (M, N), is_hermitian)
+        if t.layout == torch.sparse_csr:
+            if t.dense_dim() != 0:
+                raise RuntimeError("SparseLinearOperator.from_torch: hybrid CSR tensors are not supported")
+            crow, col, vals = t.crow_indices(), t.col_indices(), t.values()
+            if t.dim() == 2:
+                return cls(crow, col, vals, tuple(t.shape), is_hermitian)
+            bshape = tuple(t.shape[:-2])
+            crow2, col2 = crow.reshape(-1, crow.shape[-1]), col.reshape(-1, col.shape[-1])
+            if not (bool((crow2 == crow2[:1]).all()) and bool((col2 == col2[:1]).all())):
+                raise RuntimeError("SparseLinearOperator.from_torch: the members of a batched CSR tensor must share "
+                                   "one sparsity pattern")
+            return cls(crow2[0], col2[0], vals.reshape(*bshape, -1), tuple(t.shape), is_hermitian)
+        raise RuntimeError("SparseLinearOperator.from_torch: expected a sparse CSR or COO tensor, got layout %s"
+                           % t.layout)
+
+    def _apply(self, x, trans):
+        if _native_real_dtype(self.values) and x.dtype == self.values.dtype:
+            return _CsrMM.apply(self.values, x, self._pattern, trans)
+        return csr_apply_torch(self.crow, self.col, self.values, x, self.shape[-2], self.shape[-1], trans,
+                               row_of=self._pattern.row_of)
+
+    def _mv(self, x):
+        return self._apply(x.unsqueeze(-1), False).squeeze(-1)
+
+    def _mm(self, x):
+        return self._apply(x, False)
+
+    def _rmv(self, x):
+        return self._apply(x.unsqueeze(-1), True).squeeze(-1)
+
+    def _rmm(self, x):
+        return self._apply(x, True)
+
+    def _fullmatrix(self):
+        M, N = self.shape[-2:]
+        v = self.values
+        dense = torch.zeros((*v.shape[:-1], M * N), dtype=v.dtype, device=v.device)
+        lin = self._pattern.row_of.to(torch.int64) * N + self.col.to(torch.int64)
+        dense = dense.index_add(-1, lin, v).reshape(*v.shape[:-1], M, N)
+        return dense.expand(*self.shape)
+
+    def _getparamnames(self, prefix=""):
+        return [prefix + "values"]
 
 
 # ------------------------------------------------------------------------ helpers
