@@ -900,6 +900,9 @@ def symm_wide_ok(A, X):
 
 def _symm_wide_args(A, X, out):
     B, P, N = X.shape
+    if A.dtype != torch.float32 or X.dtype != torch.float32 or out.dtype != torch.float32:
+        raise _capi.NativeLibraryError("K1sw serves float32 operators and panels only, got %s / %s / %s"
+                                       % (A.dtype, X.dtype, out.dtype))
     if A.dim() == 2:
         lda, sA = A.stride(0), 0
     else:
