@@ -171,7 +171,7 @@ def test_cholqr_kernel(dev, dtype, q, with_m, shift):
     G = torch.matmul(Qc.transpose(-2, -1).conj(), MQc)
     orth = (G - torch.eye(q, dtype=c128)).abs().max().item()
     # (the shifted pass only conditions the block: orthonormal to O(shift cond^2))
-    assert orth <= (1e-6 if shift else 1e-13) if dtype == c128 else 1e-4
+    assert orth <= ((1e-6 if shift else 1e-13) if dtype == c128 else 1e-4)
     if with_m:                                                               # MW transformed alike
         assert (MWd.cpu().to(c128) - MQc.transpose(-2, -1)).abs().max().item() <= (1e-12 if dtype == c128 else 1e-4)
     # same span: W = Q (Q^H M W)

@@ -105,8 +105,13 @@ __global__ __launch_bounds__(HERM_THREADS) void herm_eigh_kernel(
   T* lu = ws + (long)b * 5 * n * p;
   const T eps = HermEps<T>::eps;
 
+  // (the diagonal is taken as real here, as zhetd2 does: an imaginary part handed over must not reach w = tau A22 v)
   for (int i = wave; i < n; i += nw)
-    for (int c = lane; c <= i; c += 64) cst(S, pk(i, c), cld(Tb, (long)i * ldt + c));
+    for (int c = lane; c <= i; c += 64) {
+      cx<T> a = cld(Tb, (long)i * ldt + c);
+      if (c == i) a.im = T(0);
+      cst(S, pk(i, c), a);
+    }
   __syncthreads();
 
   // ---- 1. Householder tridiagonalisation (zhetd2, lower): A <- H_j^H A H_j, H_j = I - tau_j v v^H -----------------
