@@ -278,6 +278,27 @@ int xk_csr_sddmm_f64(const int* row_of, const int* col, const double* U, const d
                      int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
 int xk_csr_sddmm_f32(const int* row_of, const int* col, const float* U, const float* W, float* G, int nnz, int B,
                      int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
+/* Complex values (c128 / c64): the same two products on interleaved (re, im) data, the same row bins, segments and
+ *   fixed summation order (re and im go through the same tree).  val, ws, X, Y, U, W, G point to interleaved complex;
+ *   sV, ldx, sX, ldy, sY, ldu, sU, ldw, sW, sG and the size of ws count WHOLE COMPLEX ELEMENTS.  Every element is
+ *   read and written as one 16-byte (c128) / 8-byte (c64) access, so the base pointers must be aligned to one complex
+ *   element; a slice of a complex array always is, and there is no alignment contract beyond that.
+ * xk_csr_mm_c*:    Y[b,c,i] = sum_k op(val[b*sV + (perm ? perm[k] : k)]) X[b,c,idx[k]], op = conj when conj_val != 0.
+ *   A x is the CSR view with conj_val = 0, A^H x the CSC view with conj_val = 1 (the values are never copied).
+ * xk_csr_sddmm_c*: G[b,k] = sum_c U[b,c,row_of[k]] conj(W[b,c,col[k]])  (the values gradient "gy x^H" sampled at the
+ *   pattern; adjoint apply: U = x, W = grad y). */
+int xk_csr_mm_c128(const int* ptr, const int* idx, const int* perm, const double* val, long sV, const int* rows,
+                   const int* bin_off, const int* seg_q, const int* seg_off, int nseg, double* ws, const double* X,
+                   double* Y, int B, int Mout, int Nin, int C, long ldx, long sX, long ldy, long sY, int conj_val,
+                   void* stream);
+int xk_csr_mm_c64(const int* ptr, const int* idx, const int* perm, const float* val, long sV, const int* rows,
+                  const int* bin_off, const int* seg_q, const int* seg_off, int nseg, float* ws, const float* X,
+                  float* Y, int B, int Mout, int Nin, int C, long ldx, long sX, long ldy, long sY, int conj_val,
+                  void* stream);
+int xk_csr_sddmm_c128(const int* row_of, const int* col, const double* U, const double* W, double* G, int nnz, int B,
+                      int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
+int xk_csr_sddmm_c64(const int* row_of, const int* col, const float* U, const float* W, float* G, int nnz, int B,
+                     int M, int N, int C, long ldu, long sU, long ldw, long sW, long sG, void* stream);
 
 /* ---- operator gradients of the implicit backward passes (streaming writes) -----------------------
  * The backward of solve / symeig / rootfinder ends with a VJP through the operator apply

@@ -7,8 +7,16 @@ spent in the operator product.
                                                                             rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
     python scripts/sparse_bench.py --merge-pmc <dir> --out <f>              add measured / algorithmic traffic
     python scripts/sparse_bench.py --probe-interleaved <lib> --out <f>      gather option (b) on a measurement build
+    python scripts/sparse_bench.py --dtype c128 --dtype c64 --out profiles/csr_mm_complex.json
+                                                                            complex values: the native apply against
+                                                                            the torch expression (csr_apply_torch, what
+                                                                            a complex operator ran before the complex
+                                                                            kernels) and torch.sparse.mm, same process
+    python scripts/sparse_bench.py --davidson native|torch-expression       one complex davidson call, for
+                                                                            rocprofv3 --kernel-trace --stats
 
-Algorithmic bytes of one apply: (M+1)*4 + nnz*4 + B*nnz*s + B*P*N*s + B*P*M*s (8 TB/s peak)."""
+Algorithmic bytes of one apply: (M+1)*4 + nnz*4 + B*nnz*s + B*P*N*s + B*P*M*s (8 TB/s peak), s = 8 / 16 / 8 bytes
+for f64 / c128 / c64."""
 import argparse
 import csv
 import json
@@ -74,20 +82,48 @@ def _timed(fn, calls, warmup):
     return ts[len(ts) // 2]
 
 
-def workloads(dev):
+DTYPES = {"f64": ("float64", 8), "c128": ("complex128", 16), "c64": ("complex64", 8)}
+
+
+def _randn(shape, g, dev, dtype):
     import torch
-    crow, col, val = poisson7(256, dev)
+    if dtype.is_complex:
+        return torch.view_as_complex(torch.randn(*shape, 2, generator=g, device=dev, dtype=torch.float64)).to(dtype)
+    return torch.randn(*shape, generator=g, device=dev, dtype=torch.float64).to(dtype)
+
+
+def phase_poisson7(n, dev, dtype):
+    """the 7-point operator with a complex phase on every hop (Peierls phases of a uniform field): Hermitian,
+    diagonal 6, hop (i -> j) = -exp(i theta_ij), theta_ji = -theta_ij"""
+    import torch
+    crow, col, val = poisson7(n, dev)
+    N = n ** 3
+    rows = torch.repeat_interleave(torch.arange(N, device=dev), (crow[1:] - crow[:-1]))
+    d = col.to(torch.int64) - rows
+    theta = 0.05 * torch.sign(d).double() * ((rows + col.to(torch.int64)) % n).double()      # antisymmetric in (i, j)
+    v = torch.where(d == 0, torch.full_like(theta, 6.0).to(torch.complex128), -torch.exp(1j * theta))
+    return crow, col, v.to(dtype)
+
+
+def workloads(dev, dtype_name="f64"):
+    import torch
+    dtype = getattr(torch, DTYPES[dtype_name][0])
+    if dtype.is_complex:
+        crow, col, val = phase_poisson7(256, dev, dtype)
+    else:
+        crow, col, val = poisson7(256, dev)
     for P in (1, 6, 16):
         yield "poisson7_256^3_P%d" % P, crow, col, val.unsqueeze(0), 1, P
+    if dtype.is_complex:
+        yield "poisson7_256^3_P6_B8", crow, col, val.unsqueeze(0).repeat(8, 1), 8, 6
     N = 1 << 22
     crow, col = random_pattern(N, 32, dev)
     g = torch.Generator(device=dev).manual_seed(3)
     for B in (1, 8):
-        yield "random32_2^22_B%d" % B, crow, col, torch.randn(B, col.numel(), generator=g, device=dev,
-                                                              dtype=torch.float64), B, 1
+        yield "random32_2^22_B%d" % B, crow, col, _randn((B, col.numel()), g, dev, dtype), B, 1
     N = 1 << 21
     crow, col = powerlaw_pattern(N, dev)
-    yield "powerlaw_2^21", crow, col, torch.randn(1, col.numel(), generator=g, device=dev, dtype=torch.float64), 1, 1
+    yield "powerlaw_2^21", crow, col, _randn((1, col.numel()), g, dev, dtype), 1, 1
 
 
 def run(args):
@@ -98,24 +134,46 @@ def run(args):
     dev = torch.device("cuda:0")
     rec = {"peak_bytes_per_s": HBM, "gather_form": "element gathers straight from the panel vectors (option a)",
            "kernel": [], "solver": []}
-    for wi, (name, crow, col, val, B, P) in enumerate(workloads(dev)):
+    dtypes = args.dtype or ["f64"]
+    gx = torch.Generator(device=dev).manual_seed(11)
+    for dtype_name in dtypes:
+        run_dtype(args, rec, dev, dtype_name, gx)
+    if args.pmc_only:
+        return
+    if dtypes == ["f64"]:
+        rec["solver"] = solver_runs(dev)
+    else:
+        rec["device"] = torch.cuda.get_device_name(0)
+        rec["method"] = ("HIP events around one call, median of %d after %d warm-up calls, one process, nothing "
+                         "else running on the device" % (args.calls, args.warmup))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+def run_dtype(args, rec, dev, dtype_name, gx):
+    import torch
+    from xitorch_amd import kernels as K
+    from xitorch_amd.linop import SparseLinearOperator, csr_apply_torch
+    from xitorch_amd.linalg._panel import pad_len
+    dtype, s = getattr(torch, DTYPES[dtype_name][0]), DTYPES[dtype_name][1]
+    for wi, (name, crow, col, val, B, P) in enumerate(workloads(dev, dtype_name)):
         if args.only is not None and wi != args.only:
             continue
         M = N = crow.numel() - 1
         A = SparseLinearOperator(crow, col, val[0] if val.shape[0] == 1 else val, (M, N))
         pat = A._pattern
         nnz = col.numel()
-        X = torch.randn(B, P, pad_len(N), dtype=torch.float64, device=dev)[:, :, :N]
-        Y = torch.empty(B, P, pad_len(M), dtype=torch.float64, device=dev)[:, :, :M]
+        X = _randn((B, P, pad_len(N)), gx, dev, dtype)[:, :, :N]
+        Y = torch.empty(B, P, pad_len(M), dtype=dtype, device=dev)[:, :, :M]
         fn = lambda: K.csr_mm(pat, val, X, out=Y)
         if args.pmc_only:
             fn()
             torch.cuda.synchronize()
             continue
         ms = _timed(fn, args.calls, args.warmup)
-        s = 8
         alg = (M + 1) * 4 + nnz * 4 + B * nnz * s + B * P * N * s + B * P * M * s
-        row = {"workload": name, "M": M, "nnz": nnz, "B": B, "P": P, "bins": pat.csr().bin_counts,
+        row = {"workload": name, "dtype": dtype_name, "M": M, "nnz": nnz, "B": B, "P": P, "bins": pat.csr().bin_counts,
                "ms": round(ms, 4), "alg_bytes": alg, "TB_s": round(alg / ms / 1e9, 3),
                "frac_of_8TBs": round(alg / (ms * 1e-3) / HBM, 3)}
         if B == 1:
@@ -124,17 +182,29 @@ def run(args):
                 xd = X[0].transpose(0, 1).contiguous()
                 tms = _timed(lambda: torch.sparse.mm(S, xd), args.calls, args.warmup)
                 row["torch_sparse_mm_ms"] = round(tms, 4)
+                del S, xd
             except Exception as e:          # recorded, not fatal: the library baseline is optional
                 row["torch_sparse_mm"] = "did not run: %s" % str(e).splitlines()[0][:160]
+        if dtype.is_complex:
+            # the path a complex operator took before the complex kernels: the torch expression on the (N, P) view of
+            # the same panel, result copied back into the panel (what PanelOperator's generic branch does)
+            xv = X.transpose(1, 2)
+            vals = val[0] if val.shape[0] == 1 else val
+
+            def torch_expr():
+                y = csr_apply_torch(crow, col, vals, xv, M, N, False, row_of=pat.row_of)
+                Y.copy_(y.transpose(1, 2))
+            row["torch_expr_temp_bytes"] = B * nnz * P * s
+            try:
+                tms = _timed(torch_expr, max(3, args.calls // 4), 1)
+                row["torch_expr_ms"] = round(tms, 4)
+                row["native_over_torch_expr"] = round(ms / tms, 4)
+            except Exception as e:          # out of memory: the (B, nnz, P) temporary does not fit
+                row["torch_expr"] = "did not run: %s" % str(e).splitlines()[0][:160]
+            torch.cuda.empty_cache()
         rec["kernel"].append(row)
         print(json.dumps(row), flush=True)
         del A, pat, X, Y
-    if args.pmc_only:
-        return
-    rec["solver"] = solver_runs(dev)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(rec, f, indent=1)
 
 
 def solver_runs(dev):
@@ -181,6 +251,49 @@ def solver_runs(dev):
            "share_in_csr_mm": round(op / tot, 3), "max_eval_err": float((ev - d[:6]).abs().max())}
     print(json.dumps(row), flush=True)
     out.append(row)
+    return out
+
+
+def davidson_run(which, n=128, neig=6, niter=40):
+    """One complex128 davidson call (lowest `neig` of the complex-phase 7-point operator on an n^3 grid, `niter`
+    iterations, no stopping before) for a kernel trace.  which = "native": the SparseLinearOperator as it is;
+    "torch-expression": the same operator applied by csr_apply_torch through the generic panel branch, the path
+    complex CSR operators took before the complex kernels."""
+    import time
+    import torch
+    from xitorch_amd.linop import LinearOperator, SparseLinearOperator, csr_apply_torch
+    from xitorch_amd.linalg.native_eig import davidson
+    dev = torch.device("cuda:0")
+    crow, col, val = phase_poisson7(n, dev, torch.complex128)
+    N = n ** 3
+    A = SparseLinearOperator(crow, col, val, (N, N), is_hermitian=True)
+    if which != "native":
+        pat = A._pattern
+
+        class TorchExpression(LinearOperator):
+            def __init__(self):
+                super().__init__((N, N), is_hermitian=True, dtype=val.dtype, device=val.device)
+
+            def _mv(self, x):
+                return self._mm(x.unsqueeze(-1)).squeeze(-1)
+
+            def _mm(self, x):
+                return csr_apply_torch(pat.crow, pat.col, val, x, N, N, False, row_of=pat.row_of)
+
+            def _getparamnames(self, prefix=""):
+                return []
+        A = TorchExpression()
+    out = None
+    for phase in ("warm", "timed"):
+        tr = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev, _ = davidson(A, neig, "lowest", min_eps=0.0, max_niter=niter, trace=tr)
+        torch.cuda.synchronize()
+        out = {"solver": "davidson lowest %d, complex-phase 7-point %d^3 c128, %d iterations" % (neig, n, niter),
+               "operator": which, "panel_kernel": tr["panel_kernel"], "napply": tr["napply"],
+               "ms": round((time.perf_counter() - t0) * 1e3, 2), "lowest": float(ev.min())}
+    print(json.dumps(out), flush=True)
     return out
 
 
@@ -265,8 +378,18 @@ if __name__ == "__main__":
     ap.add_argument("--only", type=int, help="run workload number ONLY (0-based), with --pmc-only")
     ap.add_argument("--merge-pmc")
     ap.add_argument("--probe-interleaved", help="measurement build (-DXK_CSR_PROBE_INTERLEAVED) to compare against")
+    ap.add_argument("--dtype", action="append", choices=sorted(DTYPES),
+                    help="value type of the timed record (repeatable; default f64)")
+    ap.add_argument("--davidson", choices=["native", "torch-expression"],
+                    help="one complex128 davidson call on the complex-phase 7-point operator, nothing else")
     a = ap.parse_args()
-    if a.probe_interleaved:
+    if a.davidson:
+        row = davidson_run(a.davidson)
+        if a.out:
+            rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+            rec.setdefault("solver", []).append(row)
+            json.dump(rec, open(a.out, "w"), indent=1)
+    elif a.probe_interleaved:
         rows = probe_interleaved(a.probe_interleaved, a.calls, a.warmup)
         if a.out:
             rec = json.load(open(a.out)) if os.path.exists(a.out) else {}

@@ -126,6 +126,9 @@ def _declare(L):
         sigs["xk_dense_outer_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
         sigs["xk_csr_mm_" + sfx] = (I, [P, P, P, P, Lg, P, P, P, P, I, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, P])
         sigs["xk_csr_sddmm_" + sfx] = (I, [P, P, P, P, P, I, I, I, I, I, Lg, Lg, Lg, Lg, Lg, P])
+    for sfx in ("c128", "c64"):
+        sigs["xk_csr_mm_" + sfx] = (I, [P, P, P, P, Lg, P, P, P, P, I, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, I, P])
+        sigs["xk_csr_sddmm_" + sfx] = (I, [P, P, P, P, P, I, I, I, I, I, Lg, Lg, Lg, Lg, Lg, P])
     for sfx in ("f64", "f32"):
         sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
         sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])

@@ -418,13 +418,18 @@ def banded_grad(U, W, nd, out=None, accumulate=False):
 
 # --------------------------------------------------------------------------- CSR sparse operator
 def csr_mm(pat, values, X, out=None, trans=False):
-    """Y[b,c,:] = A_b X[b,c,:] (trans: A_b^T X[b,c,:]) for a CSR operator whose pattern `pat` (linop._CsrPattern:
+    """Y[b,c,:] = A_b X[b,c,:] (trans: A_b^H X[b,c,:]) for a CSR operator whose pattern `pat` (linop._CsrPattern:
     int32 device index arrays and the row bins) is shared by the batch.  values (B or 1, nnz) contiguous rows,
-    X panel-major (B, C, N) (trans: (B, C, M)); returns Y (B, C, M) (trans: (B, C, N))."""
+    X panel-major (B, C, N) (trans: (B, C, M)); returns Y (B, C, M) (trans: (B, C, N)).  fp64 / fp32 / complex128 /
+    complex64; complex tensors must be resolved (no lazy conjugation bit) — the adjoint's conjugation of the values
+    is the kernel's conj_val flag, nothing is copied."""
     require_device(values, "values")
     require_device(X, "panel")
     if values.dtype != X.dtype:
         raise _capi.NativeLibraryError("dtype mismatch %s vs %s" % (values.dtype, X.dtype))
+    cplx = X.is_complex()
+    if cplx:
+        _require_resolved("csr_mm", values, X, out)
     B, C, nin = X.shape
     v = pat.csc() if trans else pat.csr()
     if nin != v.n_in:
@@ -446,17 +451,28 @@ def csr_mm(pat, values, X, out=None, trans=False):
     rc = fn("xk_csr_mm_" + suffix(X.dtype))(ptr(v.ptr), ptr(v.idx), ptr(v.perm), ptr(values), sV, ptr(v.rows),
                                              v.bin_off, ptr(v.seg_q), ptr(v.seg_off), v.nseg, ptr(ws), ptr(X),
                                              ptr(out), B, v.n_out, nin, C, ldx if C > 1 else max(ldx, nin), sX,
-                                             ldy if C > 1 else max(ldy, v.n_out), sY, stream_ptr())
+                                             ldy if C > 1 else max(ldy, v.n_out), sY,
+                                             *(((1 if trans else 0),) if cplx else ()), stream_ptr())
     check(rc, "xk_csr_mm")
     return out
 
 
+def _require_resolved(what, *tensors):
+    for t in tensors:
+        if t is not None and (t.is_conj() or t.is_neg()):
+            raise _capi.NativeLibraryError("%s: complex tensors must be resolved (resolve_conj / resolve_neg) before "
+                                           "they reach the kernel" % what)
+
+
 def csr_sddmm(pat, U, W, out=None):
-    """G[b,k] = sum_c U[b,c,row_k] W[b,c,col_k]  — the values gradient of the CSR apply (y = A x: U = grad y, W = x;
-    y = A^T x: U = x, W = grad y).  U (B, C, M), W (B, C, N) panel-major; returns G (B, nnz).  Batch dims the values
-    do not have are folded into C by the caller, so the kernel sums them in its fixed order."""
+    """G[b,k] = sum_c U[b,c,row_k] conj(W[b,c,col_k])  — the values gradient of the CSR apply (y = A x: U = grad y,
+    W = x; y = A^H x: U = x, W = grad y); for real dtypes the conjugation is void.  U (B, C, M), W (B, C, N)
+    panel-major; returns G (B, nnz).  Batch dims the values do not have are folded into C by the caller, so the
+    kernel sums them in its fixed order.  Complex tensors must be resolved."""
     require_device(U, "panel")
     require_device(W, "panel")
+    if U.is_complex():
+        _require_resolved("csr_sddmm", U, W, out)
     B, C, M = U.shape
     if W.dim() != 3 or W.shape[:2] != U.shape[:2] or U.dtype != W.dtype or M != pat.M or W.shape[2] != pat.N:
         raise _capi.NativeLibraryError("csr_sddmm: panels (B, C, %d) / (B, C, %d) expected, got %s / %s"

@@ -7,7 +7,8 @@ out[b, c, :N] = A_b x[b, c, :N] (or A_b^H) without any layout copies for the nat
 
   MatrixLinearOperator  -> xk_dense_mm   (K1; column-oriented variant when the matrix is symmetric)
   BandedLinearOperator  -> xk_banded_mm
-  SparseLinearOperator  -> xk_csr_mm     (fp32 / fp64 values; the transpose on the pattern's CSC view)
+  SparseLinearOperator  -> xk_csr_mm     (fp32 / fp64 / complex64 / complex128 values; the adjoint on the pattern's
+                                          CSC view, complex values conjugated by the kernel)
   anything else         -> the operator's own .mm/.rmm on the (.., N, p) strided view
 """
 import torch
@@ -81,10 +82,12 @@ class PanelOperator:
                 and A.band.is_contiguous():
             self.kind = "banded"
             self.band = A.band.reshape(nA, *A.band.shape[-2:])
-        elif isinstance(A, SparseLinearOperator) and native_t(A.values) and (nA == Bt or nA == 1):
+        elif isinstance(A, SparseLinearOperator) and (native_t(A.values) or native_c(A.values)) and \
+                (nA == Bt or nA == 1):
             self.kind = "csr"
+            self.cplx = native_c(A.values)
             self.pat = A._pattern
-            self.vals = A.values.reshape(-1, A.nnz)
+            self.vals = A.values.resolve_conj().reshape(-1, A.nnz)     # (a lazily conjugated view: its numbers)
             if A.nnz > 1 and self.vals.stride(-1) != 1:
                 self.vals = self.vals.contiguous()
 

@@ -878,7 +878,7 @@ class BandedLinearOperator(LinearOperator):
 
 
 # ------------------------------------------------------------------------ native CSR sparse operator
-_CSR_BIN_EDGES = (4, 32, 1024)      # row-length bin edges of xk_csr_mm (1 / 8 / 64 / 256 lanes per row)
+_CSR_BIN_EDGES = (4, 32, 1024)      # row-length bin edges of xk_csr_mm (1 / 8 / 64 / 256 lanes per row), all dtypes
 
 
 class _CsrView:
@@ -987,16 +987,19 @@ class _CsrMM(torch.autograd.Function):
         if ctx.needs_input_grad[1] and _grad_wanted(x):
             gx = _sum_to_shape(_CsrMM.apply(values, gy, pat, not ctx.trans), x.shape)
         if ctx.needs_input_grad[0] and _grad_wanted(values):
-            # d/dval[k] = sum_c gy[row_k, c] x[col_k, c]  (trans: x[row_k, c] gy[col_k, c]) — xk_csr_sddmm
+            # d/dval[k] = sum_c gy[row_k, c] conj(x[col_k, c])  (adjoint: x[row_k, c] conj(gy[col_k, c])) — xk_csr_sddmm
+            # (torch's convention for complex gradients; y = A^H x depends on conj(val), which swaps the operands)
             gval = _CsrGrad.apply(x, gy, pat, tuple(values.shape)) if ctx.trans else \
                 _CsrGrad.apply(gy, x, pat, tuple(values.shape))
         return gval, gx, None, None
 
 
 class _CsrGrad(torch.autograd.Function):
-    """G[..., k] = sum_c u[..., row_k, c] w[..., col_k, c] reduced to the values' shape (xk_csr_sddmm): the gradient
-    of the CSR apply w.r.t. the stored values.  Batch dims the values do not have are folded into the columns, so
-    the kernel sums them in a fixed order.  Bilinear: its backward is two CSR applies with G as the values."""
+    """G[..., k] = sum_c u[..., row_k, c] conj(w[..., col_k, c]) reduced to the values' shape (xk_csr_sddmm): the
+    gradient of the CSR apply w.r.t. the stored values.  Batch dims the values do not have are folded into the
+    columns, so the kernel sums them in a fixed order.  Bilinear for real dtypes, sesquilinear for complex ones
+    (linear in u, antilinear in w): its backward is two CSR applies with G as the values, grad u = A_gg w and
+    grad w = A_gg^H u — the adjoint apply conjugates gg, which is what the antilinear slot asks for."""
 
     @staticmethod
     def forward(ctx, u, w, pat, vshape):
@@ -1004,7 +1007,7 @@ class _CsrGrad(torch.autograd.Function):
         ctx.pat = pat
         nb, FB, keep, fold = _batch_plan(vshape[:-1], u.shape[:-2], w.shape[:-2])
         up, wp = _to_panel(u, nb, FB, keep, fold), _to_panel(w, nb, FB, keep, fold)
-        g = _k.csr_sddmm(pat, up, wp)                                      # (nkeep, nnz)
+        g = _k.csr_sddmm(pat, up.resolve_conj(), wp.resolve_conj())        # (nkeep, nnz)
         return g.reshape(vshape)
 
     @staticmethod
@@ -1023,8 +1026,8 @@ def _csr_native(pat, values, x, trans):
     nout = pat.N if trans else pat.M
     r = x.shape[-1]
     nb, FB, keep, fold = _batch_plan(list(values.shape[:-1]), list(x.shape[:-2]))
-    xp = _to_panel(x, nb, FB, keep, fold)                                  # (nkeep, fold * r, nin)
-    valf = values.reshape(-1, pat.nnz)
+    xp = _to_panel(x, nb, FB, keep, fold).resolve_conj()                   # (nkeep, fold * r, nin)
+    valf = values.resolve_conj().reshape(-1, pat.nnz)   # a lazily conjugated view: the conjugated numbers
     if pat.nnz > 1 and valf.stride(-1) != 1:
         valf = valf.contiguous()
     y = _k.csr_mm(pat, valf, xp, trans=trans)
@@ -1041,9 +1044,10 @@ class SparseLinearOperator(LinearOperator):
     the batch); ``shape`` is ``(M, N)`` or ``(*B, M, N)``.  Duplicate (row, col) entries add up, columns need not be
     sorted, empty rows and nnz = 0 are legal.  The structure is validated once, here.
 
-    fp32 / fp64 values on a HIP device are applied by the xk_csr_mm HIP kernel (its transpose on a CSC view built
-    on first use) and differentiated w.r.t. the values by xk_csr_sddmm; host tensors and complex values use the
-    torch expression ``csr_apply_torch``.  Only ``values`` is a parameter (``_getparamnames``): the indices are
+    fp32 / fp64 / complex64 / complex128 values on a HIP device are applied by the xk_csr_mm HIP kernels (the
+    adjoint on a CSC view built on first use, complex values conjugated as they are loaded) and differentiated
+    w.r.t. the values by xk_csr_sddmm; host tensors and mixed dtypes use the torch expression
+    ``csr_apply_torch``.  Only ``values`` is a parameter (``_getparamnames``): the indices are
     structure, so ``uselinopparams`` and the implicit backward swap the values alone."""
 
     def __init__(self, crow_indices, col_indices, values, shape, is_hermitian=False):
@@ -1131,7 +1135,7 @@ class SparseLinearOperator(LinearOperator):
                            % t.layout)
 
     def _apply(self, x, trans):
-        if _native_real_dtype(self.values) and x.dtype == self.values.dtype:
+        if _native_dtype(self.values) and x.dtype == self.values.dtype:
             return _CsrMM.apply(self.values, x, self._pattern, trans)
         return csr_apply_torch(self.crow, self.col, self.values, x, self.shape[-2], self.shape[-1], trans,
                                row_of=self._pattern.row_of)
