@@ -523,6 +523,53 @@ int xk_cg_p_c128(const double* z, double* p, const double* Prz_new, const double
 int xk_cg_p_c64(const float* z, float* p, const float* Prz_new, const float* Prz_old, int S, int N, long ld, int nblk,
                 double eps, void* stream);
 
+/* ---- MINRES step kernels (extension: Paige & Saunders 1975; Hermitian indefinite / consistent singular systems) ----
+ * Same (S, ld) vectors, block partials and nblk as the fused Krylov kernels above; _c128 / _c64 address interleaved
+ * (re, im) storage with N and ld in complex elements.  The per-system scalars (Lanczos alpha / beta, the Givens
+ * rotation, dbar / epsln, phibar, a flag) are DOUBLES whatever the vector type: state is (2, S, xk_minres_state_len())
+ * doubles, iteration k reads slot k & 1 and xk_minres_update writes slot (k + 1) & 1.  Entry i of a slot: 0 beta,
+ * 1 previous beta, 2 cs, 3 sn, 4 dbar, 5 epsln, 6 phibar, 7 flag (0 running; frozen: 1 beta = 0, exact convergence;
+ * 2 <r2, P r2> < 0, the preconditioner is not positive definite; 3 gamma = 0), 8..11 alpha, gamma, delta, phi of the
+ * step that wrote the slot.  Frozen systems are never written again (their state is carried from slot to slot).
+ * Palpha, Pb (and Pbeta with beta_is_dot = 1) are partials written by xk_kry_dots of the same suffix — (re, im)
+ * pairs for the complex suffixes, of which the real part is used; Pbeta with beta_is_dot = 0 are the real partials
+ * xk_minres_lanczos writes.  phi2[s * xk_kry_max_partials()] receives phibar^2 (+inf with flag 2): a one-partial
+ * |r|^2 array for xk_kry_status (nblk = 1).
+ * xk_minres_init: beta = sqrt(<b, y0>) from Pb (y0 = b, or P b with a preconditioner); v = y0 / beta; slot k & 1.
+ * xk_minres_lanczos: r1 <- Av - (alpha / beta) r2 - (beta / previous beta) r1 (the caller swaps r1 and r2; r1 is not
+ *   read on a first step); Pbeta (may be NULL) <- partials of |r1|^2.
+ * xk_minres_update: beta_new = sqrt(sum Pbeta); rotation; w1 <- (v - epsln w1 - delta w2) / gamma (the caller rotates
+ *   the ring); x += phi w1; v <- y / beta_new (y = the new r2, or P r2), v <- 0 when beta_new = 0. */
+int xk_minres_state_len(void);
+int xk_minres_init_f64(const double* y0, double* v, const double* Pb, double* state, double* phi2, int S, int N, long ld,
+                       int nblk, int k, void* stream);
+int xk_minres_lanczos_f64(const double* Av, const double* r2, double* r1, const double* Palpha, const double* state,
+                          double* Pbeta, int S, int N, long ld, int nblk, int k, void* stream);
+int xk_minres_update_f64(double* v, const double* y, double* w1, const double* w2, double* x, const double* Palpha,
+                         const double* Pbeta, int beta_is_dot, double* state, double* phi2, int S, int N, long ld,
+                         int nblk, int k, void* stream);
+int xk_minres_init_f32(const float* y0, float* v, const float* Pb, double* state, float* phi2, int S, int N, long ld,
+                       int nblk, int k, void* stream);
+int xk_minres_lanczos_f32(const float* Av, const float* r2, float* r1, const float* Palpha, const double* state,
+                          float* Pbeta, int S, int N, long ld, int nblk, int k, void* stream);
+int xk_minres_update_f32(float* v, const float* y, float* w1, const float* w2, float* x, const float* Palpha,
+                         const float* Pbeta, int beta_is_dot, double* state, float* phi2, int S, int N, long ld,
+                         int nblk, int k, void* stream);
+int xk_minres_init_c128(const double* y0, double* v, const double* Pb, double* state, double* phi2, int S, int N, long ld,
+                       int nblk, int k, void* stream);
+int xk_minres_lanczos_c128(const double* Av, const double* r2, double* r1, const double* Palpha, const double* state,
+                          double* Pbeta, int S, int N, long ld, int nblk, int k, void* stream);
+int xk_minres_update_c128(double* v, const double* y, double* w1, const double* w2, double* x, const double* Palpha,
+                         const double* Pbeta, int beta_is_dot, double* state, double* phi2, int S, int N, long ld,
+                         int nblk, int k, void* stream);
+int xk_minres_init_c64(const float* y0, float* v, const float* Pb, double* state, float* phi2, int S, int N, long ld,
+                       int nblk, int k, void* stream);
+int xk_minres_lanczos_c64(const float* Av, const float* r2, float* r1, const float* Palpha, const double* state,
+                          float* Pbeta, int S, int N, long ld, int nblk, int k, void* stream);
+int xk_minres_update_c64(float* v, const float* y, float* w1, const float* w2, float* x, const float* Palpha,
+                         const float* Pbeta, int beta_is_dot, double* state, float* phi2, int S, int N, long ld,
+                         int nblk, int k, void* stream);
+
 /* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
  * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
  * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.

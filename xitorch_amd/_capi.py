@@ -141,6 +141,11 @@ def _declare(L):
         sigs["xk_kry_resid_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, P])
         sigs["xk_cg_update_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
         sigs["xk_cg_p_" + sfx] = (I, [P] * 4 + [I, I, Lg, I, D, P])
+    sigs["xk_minres_state_len"] = (I, [])
+    for sfx in ("f64", "f32", "c128", "c64"):
+        sigs["xk_minres_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
+        sigs["xk_minres_lanczos_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, I, P])
+        sigs["xk_minres_update_" + sfx] = (I, [P] * 7 + [I, P, P, I, I, Lg, I, I, P])
     sigs["xk_herm_eigh_lds_bytes"] = (Lg, [I, I, I])
     sigs["xk_herm_eigh_workspace_elems"] = (Lg, [I, I, I])
     for sfx in ("c128", "c64"):

@@ -21,10 +21,9 @@
 // consumers re-reduce the <= 64 partials of their system in a fixed order.  `_safedenom`
 // (solve.py:437-439: exact zeros become eps) is applied wherever the reference applies it.
 #include "xk_common.h"
+#include "xk_kry_layout.h"
 
 namespace xk {
-
-constexpr int KRY_MAX_PART = 64;   // partial sums per system
 
 template <typename T>
 __device__ __forceinline__ T safedenom(T v, T eps) { return v == T(0) ? eps : v; }
@@ -50,17 +49,6 @@ __device__ __forceinline__ void block_store_partial(T v, T* __restrict__ part, i
   __syncthreads();
   if (threadIdx.x == 0) part[(long)s * KRY_MAX_PART + blk] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
   __syncthreads();
-}
-
-// each block handles the contiguous element range [lo, hi) of system s
-__device__ __forceinline__ void block_range(int N, int nblk, int blk, int vn, int& lo, int& hi) {
-  const int chunks = (N + vn - 1) / vn;                 // in 16 B vectors
-  const int per = (chunks + nblk - 1) / nblk;
-  lo = blk * per * vn;
-  hi = lo + per * vn;
-  const int npad = chunks * vn;
-  if (hi > npad) hi = npad;
-  if (lo > npad) lo = npad;
 }
 
 #define XK_KRY_PROLOGUE                                    \

@@ -561,6 +561,36 @@ def broyden_axpy(out, u0=None, g0=0.0, u1=None, g1=0.0, V=None, coef=None, scale
     return out
 
 
+# --------------------------------------------------------------------------- MINRES step kernels (xk_minres.hip)
+def minres_state(S, device):
+    """zeroed per-system scalar state of the MINRES kernels: (2 slots, S, xk_minres_state_len()) doubles"""
+    return torch.zeros((2, S, fn("xk_minres_state_len")()), dtype=torch.float64, device=device)
+
+
+def minres_init(y0, v, Pb, state, phi2, S, N, ld, nblk, k):
+    """beta = sqrt(<b, y0>) from the xk_kry_dots partials Pb, v = y0 / beta, state slot k & 1, phi2 <- beta^2"""
+    require_device(v, "vector")
+    check(fn("xk_minres_init_" + suffix(v.dtype))(ptr(y0), ptr(v), ptr(Pb), ptr(state), ptr(phi2), S, N, ld, nblk,
+                                                  int(k), stream_ptr()), "xk_minres_init")
+
+
+def minres_lanczos(Av, r2, r1, Palpha, state, Pbeta, S, N, ld, nblk, k):
+    """r1 <- Av - (alpha / beta) r2 - (beta / beta_old) r1 with alpha from the partials Palpha; Pbeta <- |r1|^2
+    partials (None: not wanted).  The caller swaps the roles of r1 and r2 afterwards."""
+    require_device(r1, "vector")
+    check(fn("xk_minres_lanczos_" + suffix(r1.dtype))(ptr(Av), ptr(r2), ptr(r1), ptr(Palpha), ptr(state), ptr(Pbeta),
+                                                      S, N, ld, nblk, int(k), stream_ptr()), "xk_minres_lanczos")
+
+
+def minres_update(v, y, w1, w2, x, Palpha, Pbeta, beta_is_dot, state, phi2, S, N, ld, nblk, k):
+    """rotation k; w1 <- (v - epsln w1 - delta w2) / gamma; x += phi w1; v <- y / beta_new; state slot (k + 1) & 1;
+    phi2 <- phibar^2.  beta_is_dot: Pbeta holds xk_kry_dots partials of <r2, P r2> instead of xk_minres_lanczos' own."""
+    require_device(x, "vector")
+    check(fn("xk_minres_update_" + suffix(x.dtype))(ptr(v), ptr(y), ptr(w1), ptr(w2), ptr(x), ptr(Palpha), ptr(Pbeta),
+                                                    1 if beta_is_dot else 0, ptr(state), ptr(phi2), S, N, ld, nblk,
+                                                    int(k), stream_ptr()), "xk_minres_update")
+
+
 # --------------------------------------------------------------------------- complex operators (real embedding)
 def _as_real_matrix(A):
     """zero-copy real view (.., M, 2N) of a complex matrix (.., M, N): row i = (Re A_i0, Im A_i0, Re A_i1, ...)"""

@@ -1,4 +1,4 @@
-"""cg / bicgstab / gmres for operators that live in HOST memory.
+"""cg / bicgstab / gmres / minres for operators that live in HOST memory.
 
 Device dispatch, not a fallback: the reference runs its Krylov methods on whatever device the operator's tensors are
 on (xitorch/_impls/linalg/solve.py:69-433).  Here an operator on a HIP device is served by the HIP kernels of
@@ -20,9 +20,9 @@ from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape, ConvergenceWarning
 from xitorch_amd.dist import allreduce_max_, all_ranks_agree_true
 
-__all__ = ["cg", "bicgstab", "gmres", "scipy_gmres"]
+__all__ = ["cg", "bicgstab", "gmres", "minres", "scipy_gmres"]
 
-calls = {"cg": 0, "bicgstab": 0, "gmres": 0, "scipy_gmres": 0}        # how often each host driver ran (tests assert 0 on the GPU path)
+calls = {"cg": 0, "bicgstab": 0, "gmres": 0, "minres": 0, "scipy_gmres": 0}        # how often each host driver ran (tests assert 0 on the GPU path)
 
 
 def _nonzero(d, eps):
@@ -333,6 +333,115 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
                                          "Max norm of resid: %.3e" % (max_niter, best)))
     return xbest
+
+
+def check_minres_inputs(A, M, E):
+    """MINRES needs a Hermitian operator A - E M with real shifts: raises otherwise; returns E (real part of a complex
+    E whose imaginary part is zero when the operator is real)."""
+    if not A.is_hermitian or (M is not None and E is not None and not M.is_hermitian):
+        raise RuntimeError("minres needs Hermitian operators A and M (there is no normal-equation fallback); use "
+                           "method='bicgstab' or method='gmres' for a general operator")
+    if E is not None and E.is_complex():
+        if bool((E.imag != 0).any()):
+            raise RuntimeError("minres needs real shifts E: A - E M is not Hermitian for a complex E; use "
+                               "method='bicgstab' or method='gmres'")
+        if not A.dtype.is_complex:
+            E = E.real
+    return E
+
+
+def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1e-8, max_restart=2, verbose=False,
+           process_group=None, trace=None, **unused):
+    """MINRES (Paige & Saunders 1975) in host memory for Hermitian, possibly indefinite or consistent singular
+    operators; options, stopping rule and true-residual confirmation as `native_krylov.minres`, each fused kernel
+    replaced by the torch expression it computes.  The Lanczos / rotation scalars are float64 `(*batch, 1, ncols)`."""
+    calls["minres"] += 1
+    E = check_minres_inputs(A, M, E)
+    if max_niter is None:
+        max_niter = int(1.5 * A.shape[-1])
+    bdims = _batchdims(A, B, E, M)
+    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
+        return _zero_solution(A, B, bdims)
+    prob = _HostProblem(A, B, E, M, bdims, True, need_hermit=True)
+    pre = _precond(precond)
+    stop = _stop_of(prob, rtol, atol)
+    dt, f64 = prob.dtype, torch.float64
+    one = torch.ones((*prob.bdims, 1, prob.nc), dtype=f64)
+    safe = lambda d: torch.where(d == 0, one, d)
+    x = torch.zeros(prob.shape, dtype=dt)
+    r2 = prob.rhs
+    k, nrestart, hist = 0, 0, []
+    converged, best = False, float("inf")
+    stop_rec, rtrue_norm = stop, None
+    while True:
+        y = pre(r2) if pre is not None else r2
+        bb = _coldot(r2, y).real.to(f64)
+        if bool((bb < 0).any()):
+            raise RuntimeError("minres: <r, P r> < 0: the preconditioner is not positive definite")
+        beta = bb.sqrt()
+        frozen = beta == 0
+        v = torch.where(frozen, torch.zeros_like(y), y * (1.0 / safe(beta)).to(dt))
+        oldb, cs, sn = torch.zeros_like(beta), -torch.ones_like(beta), torch.zeros_like(beta)
+        dbar, epsln, phibar = torch.zeros_like(beta), torch.zeros_like(beta), beta
+        w1, w2, r1 = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
+        if rtrue_norm is not None:
+            # restart: the recurrence has to fall by the factor the TRUE norm still has to fall by (with a
+            # preconditioner phibar is the P-norm of the residual, not its 2-norm), and by 2 for safety
+            stop_rec = torch.minimum(stop_rec, (0.5 * beta * stop / safe(rtrue_norm.to(f64))).to(stop.dtype))
+        _, nbad = _status(phibar.to(stop.dtype), stop_rec, process_group)
+        rec_ok = nbad == 0
+        while not rec_ok and k < max_niter:
+            Av = prob.apply(v)
+            alpha = _coldot(v, Av).real.to(f64)
+            c1 = torch.where(oldb != 0, beta / safe(oldb), torch.zeros_like(beta))
+            ynew = (Av - (alpha / safe(beta)).to(dt) * r2) - c1.to(dt) * r1
+            r1, r2 = r2, ynew
+            y = pre(r2) if pre is not None else r2
+            bb = _coldot(r2, y).real.to(f64)
+            if bool(((bb < 0) & ~frozen).any()):
+                raise RuntimeError("minres: <r, P r> < 0: the preconditioner is not positive definite")
+            bnew = bb.clamp(min=0).sqrt()
+            delta = cs * dbar + sn * alpha
+            gbar = sn * dbar - cs * alpha
+            gamma = torch.sqrt(gbar * gbar + bnew * bnew)
+            stuck = (gamma == 0) & ~frozen                          # no descent left in the Krylov space
+            live = ~(frozen | stuck)
+            csn, snn = gbar / safe(gamma), bnew / safe(gamma)
+            phi = csn * phibar
+            w = ((v - epsln.to(dt) * w1) - delta.to(dt) * w2) * (1.0 / safe(gamma)).to(dt)
+            x = torch.where(live, x + phi.to(dt) * w, x)
+            phibar = torch.where(live, snn * phibar, phibar)
+            w1, w2 = w2, w
+            done = live & (bnew == 0)                               # exact convergence: freeze, no eps replacement
+            frozen = frozen | stuck | done
+            v = torch.where(frozen, torch.zeros_like(y), y * (1.0 / safe(bnew)).to(dt))
+            epsln, dbar, oldb, beta, cs, sn = sn * bnew, -cs * bnew, beta, bnew, csn, snn
+            k += 1
+            mx, nbad = _status(phibar.to(stop.dtype), stop_rec, process_group)
+            hist.append(mx)
+            if verbose and (k < 10 or k % 10 == 0):
+                print("%4d: |dy|=%.3e" % (k, mx))
+            if nbad == 0:
+                rec_ok = True
+            elif mx != mx or mx == float("inf"):
+                break
+        rtrue = prob.rhs - prob.apply(x)                            # confirmation on the true residual
+        rtrue_norm = _colnorm(rtrue)
+        best, nbad = _status(rtrue_norm, stop, process_group)
+        if nbad == 0:
+            converged = True
+            break
+        if not rec_ok or nrestart >= max_restart or k >= max_niter:
+            break
+        nrestart += 1
+        r2 = rtrue
+    if trace is not None:
+        trace.update(niter=k, napply=prob.napply, converged=converged, best_resid=best, nrestart=nrestart,
+                     resid_history=hist)
+    if not converged:
+        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
+                                         "Max norm of resid: %.3e" % (k, best)))
+    return x
 
 
 def scipy_gmres(A, B, E=None, M=None, min_eps=1e-9, max_niter=None, **unused):

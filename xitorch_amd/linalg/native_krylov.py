@@ -1,4 +1,4 @@
-"""Linear solvers: dense `exactsolve` and the native (HIP) Krylov methods cg / bicgstab / gmres.
+"""Linear solvers: dense `exactsolve` and the native (HIP) Krylov methods cg / bicgstab / gmres / minres.
 
 Drop-in for the method functions of the reference (xitorch/_impls/linalg/solve.py): same names,
 signatures ``f(A, B, E, M, **options) -> X``, options, stopping rule
@@ -22,7 +22,7 @@ from xitorch_amd._util import bcast_shape, pad_shapes, ConvergenceWarning
 from xitorch_amd.linalg._panel import PanelOperator, pad_len, to_panel, from_panel
 from xitorch_amd.dist import allreduce_max_, all_ranks_agree_true
 
-__all__ = ["exactsolve", "custom_exactsolve", "cg", "bicgstab", "gmres", "scipy_gmres", "broyden1_solve", "get_batchdims"]
+__all__ = ["exactsolve", "custom_exactsolve", "cg", "bicgstab", "gmres", "minres", "scipy_gmres", "broyden1_solve", "get_batchdims"]
 
 
 def _in_host_memory(A):
@@ -288,10 +288,11 @@ class _Kry:
         self._c("cg_p", ptr(z), ptr(p), ptr(Prz_new), ptr(Prz_old), self.S, self.N, self.ld, self.nblk,
                 float(eps))
 
-    def check_status(self, Prr, stop, process_group=None):
-        """-> (max residual norm over all systems, number of unconverged systems): the one host sync."""
+    def check_status(self, Prr, stop, process_group=None, nblk=None):
+        """-> (max residual norm over all systems, number of unconverged systems): the one host sync.
+        nblk: partials per system held by Prr (default: the block count of the vector kernels)."""
         check(fn("xk_kry_status_" + self.rsfx)(ptr(Prr), ptr(stop), ptr(self.rnorm), ptr(self.status), self.S,
-                                               self.nblk, stream_ptr()), "xk_kry_status")
+                                               self.nblk if nblk is None else nblk, stream_ptr()), "xk_kry_status")
         # MAX over the ranks of both entries: max residual, and "someone is unconverged" (count > 0)
         allreduce_max_(self.status, process_group)
         mx, nbad = self.status.tolist()
@@ -756,6 +757,148 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
                                          "Max norm of resid: %.3e" % (max_niter, best)))
     return prob.solution(xbufs[best_i].reshape(prob.Bt, prob.nc, ld))
+
+
+# ------------------------------------------------------------------------------- MINRES
+def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1e-8, max_restart=2, verbose=False,
+           process_group=None, trace=None, **unused):
+    r"""
+    Solve the linear equations with the minimal residual method MINRES (Paige & Saunders 1975) on HIP kernels
+    (extension: the reference has no MINRES).
+
+    For Hermitian operators :math:`\mathbf{A} - e_c \mathbf{M}` that may be indefinite, or singular with a
+    consistent right-hand side (the shifted systems of the ``symeig`` backward): one operator apply per iteration, a
+    three-term recurrence (constant storage), a residual norm that never grows, and, from ``x0 = 0``, the minimum-norm
+    solution of a consistent singular system.  An exactly vanishing Lanczos norm freezes its system (exact
+    convergence); no denominator is ever replaced by an ``eps``.
+
+    Stopping rule, per system: :math:`|r| \le \max(\mathrm{rtol}\,|b|, \mathrm{atol})`, evaluated on the recurrence
+    value :math:`\bar\phi` (equal to :math:`|b - A x_k|` in exact arithmetic) with one host read per iteration.  When
+    every system passes, the true residual is computed once; a system that misses the rule is restarted from the
+    current iterate with that residual as right-hand side, at most ``max_restart`` times (with a preconditioner
+    :math:`\bar\phi` is the :math:`P`-norm of the residual: a restart therefore asks the recurrence for the reduction
+    the true norm still lacks).  The returned iterate is
+    always one whose true residual was computed; a ``ConvergenceWarning`` carries its norm when the rule is not met.
+
+    Keyword arguments
+    -----------------
+    precond: LinearOperator or None
+        Hermitian POSITIVE DEFINITE preconditioner (not checked, except that :math:`\langle r, P r\rangle < 0` raises)
+    max_niter: int or None
+        Maximum number of iterations over all restarts (default ``int(1.5 * A.shape[-1])``)
+    rtol, atol: float
+        Relative / absolute tolerance of the stopping condition w.r.t. the norm of B
+    max_restart: int
+        Maximum number of restarts after a failed true-residual confirmation
+    verbose: bool
+        Print the progress
+    process_group: torch.distributed group or None
+        batch-sharded multi-GPU run: the stopping test is all-reduced over the group
+    trace: dict or None
+        receives ``niter``, ``napply``, ``converged``, ``best_resid`` (true), ``nrestart``, ``resid_history``
+
+    ``A`` and ``M`` must be Hermitian and ``E`` real (``RuntimeError`` otherwise: use ``bicgstab`` or ``gmres``);
+    ``posdef`` is accepted and ignored.
+    """
+    from xitorch_amd.linalg import host_krylov
+    if _in_host_memory(A):
+        return host_krylov.minres(A, B, E, M, precond=precond, max_niter=max_niter, rtol=rtol, atol=atol,
+                                  max_restart=max_restart, verbose=verbose, process_group=process_group, trace=trace)
+    E = host_krylov.check_minres_inputs(A, M, E)
+    if max_niter is None:
+        max_niter = int(1.5 * A.shape[-1])
+    bdims = get_batchdims(A, B, E, M)
+    # (sharded runs: every rank takes this shortcut or none does — the loop below contains collectives)
+    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
+        return _zeros_like_solution(A, B, bdims)
+    prob = _Problem(A, B, E, M, bdims, True, need_hermit=True)       # Hermitian: never the normal equations
+    if trace is not None and trace.get("k1_events") is not None:
+        prob.opA.events = trace["k1_events"]          # measurement: HIP events around every operator apply
+    kr = _Kry(prob)
+    pre = _precond(precond, prob)
+    stop = _stop_vector(prob, rtol, atol)
+    S, N, ld, nblk = prob.S, prob.N, prob.ld, kr.nblk
+
+    x, v, Av, tmp, rtrue = (prob.new() for _ in range(5))
+    r1, r2 = prob.new(), prob.rhs.clone()                            # x0 = 0: the first right-hand side is B
+    w1, w2 = prob.new(), prob.new()
+    ybuf = prob.new() if pre is not None else None
+    state = K.minres_state(S, prob.device)
+    Palpha, Pdot = kr.partial(), (kr.partial() if pre is not None else None)
+    Pbeta, Pphi, Prr = kr.partial_real(), kr.partial_real(), kr.partial_real()
+    flagged = torch.zeros((1,), dtype=torch.float64, device=prob.device)
+
+    stop_rec = stop
+
+    def status(k):
+        """the iteration's one host read; a non-finite maximum is looked into: the preconditioner flag raises"""
+        mx, nbad = kr.check_status(Pphi, stop_rec, process_group, nblk=1)
+        if mx != mx or mx == float("inf"):
+            flagged[0] = (state[k & 1, :, 7] == 2).any().double()
+            allreduce_max_(flagged, process_group)
+            if flagged.item() != 0:
+                raise RuntimeError("minres: <r, P r> < 0: the preconditioner is not positive definite")
+        return mx, nbad
+
+    k, nrestart, hist = 0, 0, []
+    converged, best = False, float("inf")
+    while True:
+        y = r2
+        if pre is not None:
+            pre.apply(r2, ybuf)
+            y = ybuf
+        kr.dots(r2, y, Palpha)                                       # <b, P b>
+        K.minres_init(y, v, Palpha, state, Pphi, S, N, ld, nblk, k)
+        if nrestart > 0:
+            # restart: the recurrence has to fall by the factor the TRUE norm still has to fall by (with a
+            # preconditioner phibar is the P-norm of the residual, not its 2-norm), and by 2 for safety
+            rt = rtrue_norm.double()
+            scaled = 0.5 * state[k & 1, :, 6] * stop.double() / torch.where(rt == 0, torch.ones_like(rt), rt)
+            stop_rec = torch.minimum(stop_rec, scaled.to(stop.dtype)).contiguous()
+        mx, nbad = status(k)
+        rec_ok = nbad == 0
+        while not rec_ok and k < max_niter:
+            sh = prob.apply(v, Av, defer=True)
+            kr.dots(v, Av, Palpha, shift=sh)                         # alpha = <v, A v>, shift folded in
+            K.minres_lanczos(Av, r2, r1, Palpha, state, Pbeta if pre is None else None, S, N, ld, nblk, k)
+            r1, r2 = r2, r1
+            y = r2
+            if pre is not None:
+                pre.apply(r2, ybuf)
+                kr.dots(r2, ybuf, Pdot)                              # beta^2 = <r2, P r2>
+                y = ybuf
+            K.minres_update(v, y, w1, w2, x, Palpha, Pbeta if pre is None else Pdot, pre is not None, state, Pphi,
+                            S, N, ld, nblk, k)
+            w1, w2 = w2, w1
+            k += 1
+            mx, nbad = status(k)
+            hist.append(mx)
+            if verbose and (k < 10 or k % 10 == 0):
+                print("%4d: |dy|=%.3e" % (k, mx))
+            if nbad == 0:
+                rec_ok = True
+            elif mx != mx or mx == float("inf"):
+                break
+        prob.apply(x, tmp)                                           # confirmation on the true residual
+        kr.resid(prob.rhs, tmp, rtrue, None, Prr, None)
+        best, nbad = kr.check_status(Prr, stop, process_group)
+        if nbad == 0:
+            converged = True
+            break
+        if not rec_ok or nrestart >= max_restart or k >= max_niter:
+            break
+        nrestart += 1                                                # restart from x with the true residual
+        rtrue_norm = kr.rnorm.clone()
+        r2.copy_(rtrue)
+        w1.zero_()
+        w2.zero_()
+    if trace is not None:
+        trace.update(niter=k, napply=prob.napply, converged=converged, best_resid=best, nrestart=nrestart,
+                     resid_history=hist)
+    if not converged:
+        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
+                                         "Max norm of resid: %.3e" % (k, best)))
+    return prob.solution(x)
 
 
 def scipy_gmres(A, B, E=None, M=None, min_eps=1e-9, max_niter=None, **unused):

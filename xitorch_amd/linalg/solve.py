@@ -1,7 +1,7 @@
 """solve — functional front-end of the linear-equation path  A X = B  /  A X - M X E = B.
 
 Same signature, defaults, argument checks and adjoint backward as the reference
-(xitorch/linalg/solve.py:13-243).  The iterative methods ("cg", "bicgstab", "gmres",
+(xitorch/linalg/solve.py:13-243).  The iterative methods ("cg", "bicgstab", "gmres", "minres",
 "broyden1") are the native HIP implementations of xitorch_amd/linalg/native_krylov.py;
 "exactsolve" is the dense `torch.linalg.solve` path.
 """
@@ -29,7 +29,8 @@ def solve(A, B, E=None, M=None, bck_options={}, method=None, **fwd_options):
         Options of the solver used in the backward pass
     method: str or callable or None
         ``None`` picks ``"exactsolve"`` for dense matrices / ``na <= 5``, else ``"cg"`` for Hermitian
-        and ``"bicgstab"`` for general operators.  A callable ``f(A, B, E, M, **fwd_options) -> X``
+        and ``"bicgstab"`` for general operators.  ``"minres"`` (extension, never picked by default) is
+        made for Hermitian indefinite or consistent singular operators.  A callable ``f(A, B, E, M, **fwd_options) -> X``
         plugs in a user method.
     **fwd_options
         Method-specific options
@@ -95,6 +96,7 @@ class _SolveFunction(torch.autograd.Function):
                     "cg": nk.cg,
                     "bicgstab": nk.bicgstab,
                     "gmres": nk.gmres,
+                    "minres": nk.minres,
                     "scipy_gmres": nk.scipy_gmres,
                 }
                 x = get_method("solve", methods, method)(A, B, E, M, **config)
