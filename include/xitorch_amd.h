@@ -478,6 +478,42 @@ int xk_gmres_finish_f32(float* Q, const float* c2n, long sc2, const float* inv_h
 int xk_gmres_solve_f64(const double* R, const double* g, double* y, long sy, int S, int kd, int cap, void* stream);
 int xk_gmres_solve_f32(const double* R, const double* g, float* y, long sy, int S, int kd, int cap, void* stream);
 
+/* ---- GMRES for COMPLEX systems (extension: the reference's gmres is real-only; xk_gmres_c.hip) --------------------
+ * Complex data is INTERLEAVED (re, im) storage; every pitch, stride and length counts whole COMPLEX elements.  A 16 B
+ * vector holds CV = 1 complex128 / 2 complex64 elements; pitches and strides must be multiples of CV, base pointers 16 B
+ * aligned, and the pad [N, round_up(N, CV)) of every vector zero (else XK_ERR_UNSUPPORTED where it can be checked).
+ * xk_gmres_gram: c[s, i] = sum_n conj(Q[s, i, n]) w[s, n] for i < kq (Q: sQ between systems, ldq between rows; w: sw
+ *   between systems; c: sc between systems) and c[s, kq] = (|w_s|^2, exactly 0).  Fixed-shape reduction without atomics
+ *   (repeated calls are bit-identical): every vector is cut into tiles of 1024 * CV elements, nblk MUST be
+ *   ceil(N / (1024 * CV)) (else XK_ERR_ARG; N == 0: nblk == 0 and c[s, 0..kq] = 0), scratch holds
+ *   S * nblk * (kq + 1) * 2 doubles.  Products and wave sums in
+ *   the vector's precision, everything above a wave in double.
+ * xk_lincomb: Out[b, c, :] = beta Out[b, c, :] + alpha sum_{a<k} C[b, c, a] V[b, a, :], complex C (sC between batch
+ *   members, sCc between output rows, a contiguous: the "ca" layout), REAL alpha / beta; c < P.
+ * xk_gmres_step / _finish / _solve: as the real kernels above with complex c1, c2n (c2n[s, k+1] = (|w1|^2, 0)), Q, y and
+ *   state R (S, cap+1, cap), sn (S, cap), g (S, cap+1) COMPLEX double, cs (S, cap) REAL double; inv_hn and est2 are
+ *   real (est2 = |g[k+1]|^2 for xk_kry_status_f64/_f32).  Rotation k for a = rotated h[k,k], b = h[k+1,k] >= 0:
+ *   cs = |a| / sqrt(|a|^2 + b^2), sn = (a / |a|) b / sqrt(|a|^2 + b^2) (a = 0: cs = 0, sn = 1), and
+ *   [cs, sn; -conj(sn), cs] is applied from the left.  xk_gmres_solve: kd <= 4096 (else XK_ERR_UNSUPPORTED). */
+int xk_gmres_gram_c128(const double* Q, const double* w, double* c, double* scratch, int S, int N, int kq, long ldq,
+                       long sQ, long sw, long sc, int nblk, void* stream);
+int xk_gmres_gram_c64(const float* Q, const float* w, float* c, double* scratch, int S, int N, int kq, long ldq,
+                      long sQ, long sw, long sc, int nblk, void* stream);
+int xk_lincomb_c128(const double* V, const double* C, double* Out, int B, int k, int N, int P, long ldv, long sV,
+                    long sC, long sCc, long ldo, long sO, double alpha, double beta, void* stream);
+int xk_lincomb_c64(const float* V, const float* C, float* Out, int B, int k, int N, int P, long ldv, long sV,
+                   long sC, long sCc, long ldo, long sO, double alpha, double beta, void* stream);
+int xk_gmres_step_c128(const double* c1, long sc1, const double* c2n, long sc2, int k, int cap, double* R, double* cs,
+                       double* sn, double* g, double* inv_hn, double* est2, int S, void* stream);
+int xk_gmres_step_c64(const float* c1, long sc1, const float* c2n, long sc2, int k, int cap, double* R, double* cs,
+                      double* sn, double* g, float* inv_hn, float* est2, int S, void* stream);
+int xk_gmres_finish_c128(double* Q, const double* c2n, long sc2, const double* inv_hn, int S, int N, int k, long ldq,
+                         long sQ, void* stream);
+int xk_gmres_finish_c64(float* Q, const float* c2n, long sc2, const float* inv_hn, int S, int N, int k, long ldq,
+                        long sQ, void* stream);
+int xk_gmres_solve_c128(const double* R, const double* g, double* y, long sy, int S, int kd, int cap, void* stream);
+int xk_gmres_solve_c64(const double* R, const double* g, float* y, long sy, int S, int kd, int cap, void* stream);
+
 /* ---- the same fused Krylov kernels for COMPLEX systems (complex64 = _c64, complex128 = _c128) ----------
  * The reference runs cg / bicgstab on complex operators with conjugated inner products
  * (xitorch/_impls/linalg/solve.py:441-445; _tests/test_linop_fcns.py:474-524, 631-676).  Pointers address

@@ -133,6 +133,12 @@ def _declare(L):
         sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
         sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])
         sigs["xk_gmres_solve_" + sfx] = (I, [P, P, P, Lg, I, I, I, P])
+    for sfx in ("c128", "c64"):
+        sigs["xk_gmres_gram_" + sfx] = (I, [P, P, P, P, I, I, I, Lg, Lg, Lg, Lg, I, P])
+        sigs["xk_lincomb_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, D, D, P])
+        sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
+        sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])
+        sigs["xk_gmres_solve_" + sfx] = (I, [P, P, P, Lg, I, I, I, P])
     for sfx in ("c64", "c128"):
         sigs["xk_kry_dots_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, I, P])
         sigs["xk_bicg_p_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])

@@ -117,6 +117,58 @@ def lincomb(V, C, out, k, P, coef_layout="ac", alpha=1.0, beta=0.0):
     return out
 
 
+def _cplx_vec(dtype):
+    """complex elements per 16 B vector"""
+    return 1 if dtype == torch.complex128 else 2
+
+
+def lincomb_c(V, C, out, k, P, alpha=1.0, beta=0.0, N=None):
+    """out[b,c,:] = beta*out[b,c,:] + alpha * sum_{a<k} C[b,c,a] * V[b,a,:] for COMPLEX panels (xk_lincomb_c128/_c64):
+    V (B, >=k, ld), out (B, >=P, ld) panel-major, C (B, >=P, >=k) with unit stride over a (the "ca" layout of
+    `lincomb`), alpha / beta real; N: vector length (default: the whole pitch V.shape[2]).  The projections and the
+    iterate x = Q y of the complex GMRES."""
+    require_device(V, "basis")
+    _require_resolved("lincomb_c", V, C, out)
+    if V.dtype != out.dtype or C.dtype != V.dtype or not V.is_complex():
+        raise _capi.NativeLibraryError("lincomb_c: complex V, C, out of one dtype expected")
+    if V.stride(2) != 1 or out.stride(2) != 1 or (k > 1 and C.stride(2) != 1):
+        raise _capi.NativeLibraryError("lincomb_c: unit stride along the vector / coefficient axis expected")
+    B = V.shape[0]
+    N = V.shape[2] if N is None else N
+    rc = fn("xk_lincomb_" + suffix(V.dtype))(ptr(V), ptr(C), ptr(out), B, k, N, P, V.stride(1), V.stride(0),
+                                              C.stride(0), C.stride(1), out.stride(1), out.stride(0), float(alpha),
+                                              float(beta), stream_ptr())
+    check(rc, "xk_lincomb_c")
+    return out
+
+
+def gmres_gram_tiles(N, dtype):
+    """number of fixed reduction tiles (1024 16 B vectors each) xk_gmres_gram_c* cuts a length-N complex vector into"""
+    tile = 1024 * _cplx_vec(dtype)
+    return (N + tile - 1) // tile
+
+
+def gmres_gram_c(Q, w, c, scratch, kq, N):
+    """c[s, i] = <Q[s, i], w[s]> = sum conj(Q) w for i < kq, c[s, kq] = |w_s|^2 + 0i  (xk_gmres_gram_c128/_c64).
+    Q (S, >=kq, ld), w (S, ld) (may be a row view of Q), c (S, >=kq+1) complex; scratch: float64, at least
+    S * gmres_gram_tiles(N) * (kq + 1) * 2 elements.  Fixed-shape reduction: repeated calls are bit-identical."""
+    require_device(Q, "basis")
+    _require_resolved("gmres_gram_c", Q, w, c)
+    S = Q.shape[0]
+    nblk = gmres_gram_tiles(N, Q.dtype)
+    if w.dtype != Q.dtype or c.dtype != Q.dtype or not Q.is_complex() or scratch.dtype != torch.float64:
+        raise _capi.NativeLibraryError("gmres_gram_c: complex Q, w, c of one dtype and a float64 scratch expected")
+    if Q.stride(2) != 1 or w.stride(1) != 1 or c.stride(1) != 1 or c.shape[1] < kq + 1 or Q.shape[1] < kq:
+        raise _capi.NativeLibraryError("gmres_gram_c: bad layout")
+    if scratch.numel() < S * nblk * (kq + 1) * 2:
+        raise _capi.NativeLibraryError("gmres_gram_c: scratch holds %d doubles, %d needed"
+                                       % (scratch.numel(), S * nblk * (kq + 1) * 2))
+    rc = fn("xk_gmres_gram_" + suffix(Q.dtype))(ptr(Q), ptr(w), ptr(c), ptr(scratch), S, N, kq, Q.stride(1),
+                                                 Q.stride(0), w.stride(0), c.stride(0), nblk, stream_ptr())
+    check(rc, "xk_gmres_gram")
+    return c
+
+
 def group_status(rmax, info, flag, status, orth=None):
     """status (3 doubles on the device) = {max rmax (NaN-propagating), max info, max flag or 0}: one launch instead of
     three reductions and three converting copies (the host reads it once per Davidson step, symeig.py:190-197).

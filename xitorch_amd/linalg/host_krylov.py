@@ -257,16 +257,16 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
 
 def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-8, eps=1e-12, resid_calc_every=1,
           restart=None, process_group=None, trace=None, **unused):
-    """Un-restarted GMRES in host memory (reference: gmres, solve.py:326-433; real operators only, like the
-    reference's): the same iterates, stopping rule and return value as `native_krylov.gmres` — after k Arnoldi steps
+    """Un-restarted GMRES in host memory (reference: gmres, solve.py:326-433; real and complex operators — the
+    reference's is real-only; `_coldot` conjugates its first argument, so the Hessenberg matrix of a complex operator
+    is the complex one and `torch.linalg.lstsq` solves it as it stands): the same iterates, stopping rule and return
+    value as `native_krylov.gmres` — after k Arnoldi steps
     the iterate minimises the residual over the k-dimensional Krylov space, the TRUE residual decides convergence and
     which iterate is the best one, at most min(nr, max_niter) - 1 Krylov vectors contribute.  The Hessenberg matrices
     of all systems are one batched tensor; the small least-squares problem is `torch.linalg.lstsq`, as in the
     reference (:403).  `restart=m` (extension): GMRES(m), as in the native driver."""
     calls["gmres"] += 1
     nr = A.shape[-1]
-    if A.dtype.is_complex:
-        raise NativeLibraryError("xitorch_amd gmres supports real operators only, like the reference's gmres")
     if max_niter is None:
         max_niter = int(nr)
     bdims = _batchdims(A, B, E, M)

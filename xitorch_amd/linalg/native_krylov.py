@@ -532,11 +532,17 @@ def cg(A, B, E=None, M=None, posdef=None, precond=None, max_niter=None, rtol=1e-
 # ------------------------------------------------------------------------------- GMRES
 class _GmresState:
     """Per-system Hessenberg / Givens state on the device (float64 whatever the vector dtype), growing with the basis
-    (the reference preallocates max_niter vectors and a (max_niter+1) x max_niter Hessenberg, solve.py:384-386, Q12)."""
+    (the reference preallocates max_niter vectors and a (max_niter+1) x max_niter Hessenberg, solve.py:384-386, Q12).
+    cplx: R, sn, g are complex128 (interleaved pairs for xk_gmres_*_c*), cs stays real."""
 
-    def __init__(self, S, cap, device):
+    def __init__(self, S, cap, device, cplx=False):
         self.S, self.cap, self.device = S, cap, device
+        self.zdtype = torch.complex128 if cplx else torch.float64
         z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+        if cplx:
+            zc = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device=device)
+            self.R, self.cs, self.sn, self.g = zc(S, cap + 1, cap), z(S, cap), zc(S, cap), zc(S, cap + 1)
+            return
         self.R, self.cs, self.sn, self.g = z(S, cap + 1, cap), z(S, cap), z(S, cap), z(S, cap + 1)
 
     def grow(self, need, limit):
@@ -544,7 +550,8 @@ class _GmresState:
             return
         new = min(limit, max(need, 2 * self.cap))
         z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
-        R, cs, sn, g = z(self.S, new + 1, new), z(self.S, new), z(self.S, new), z(self.S, new + 1)
+        zc = lambda *shape: torch.zeros(shape, dtype=self.zdtype, device=self.device)
+        R, cs, sn, g = zc(self.S, new + 1, new), z(self.S, new), zc(self.S, new), zc(self.S, new + 1)
         R[:, :self.cap + 1, :self.cap] = self.R
         cs[:, :self.cap], sn[:, :self.cap], g[:, :self.cap + 1] = self.cs, self.sn, self.g
         self.R, self.cs, self.sn, self.g, self.cap = R, cs, sn, g, new
@@ -554,7 +561,10 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
           resid_calc_every=1, restart=None, process_group=None, trace=None, **unused):
     r"""
     Solve the linear equations using the Generalised minimal residual method on HIP kernels
-    (reference: gmres, xitorch/_impls/linalg/solve.py:326-433; real operators only, like the reference's).
+    (reference: gmres, xitorch/_impls/linalg/solve.py:326-433).  Real and complex operators (extension: the reference's
+    gmres is real-only); for complex dtypes inner products are ``<x, y> = sum conj(x) y``, the Hessenberg matrix and
+    the Givens sines are complex, and the basis work runs on ``xk_gmres_gram_c*`` / ``xk_lincomb_c*`` /
+    ``xk_gmres_*_c*`` in place of the real kernels named below.
 
     Same iterates, same stopping rule and same return value as the reference: un-restarted GMRES from ``x0 = 0``;
     after ``k`` Arnoldi steps the iterate ``x_k`` minimises the residual over the ``k``-dimensional Krylov space; the
@@ -608,9 +618,6 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                                  resid_calc_every=resid_calc_every, restart=restart, process_group=process_group,
                                  trace=trace)
     nr, ncols = A.shape[-1], B.shape[-1]
-    if A.dtype.is_complex:
-        # the reference's own gmres is real-only as well (its tests xfail complex input, test_linop_fcns.py:479-481)
-        raise NativeLibraryError("xitorch_amd gmres supports real operators only, like the reference's gmres")
     if max_niter is None:
         max_niter = int(nr)
     bdims = get_batchdims(A, B, E, M)
@@ -634,15 +641,16 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         msteps = max_niter - 1 if max_niter > 1 else 0      # (restarted: the total is not bounded by the order)
     mcyc = msteps if restart is None else min(restart, max(msteps, 1))     # Arnoldi steps per cycle
     lazy_limit = None
-    if mcyc > 8192:
-        # xk_gmres_solve keeps the least-squares solution of a system in LDS: at most 8192 basis vectors per cycle (the
-        # dense Hessenberg of such a run is 8 S k^2 bytes long before that).  An explicit restart length beyond it is
-        # refused here; the un-restarted default (max_niter = None -> the operator's order, solve.py:389) only fails if
+    kd_max = 4096 if prob.cplx else 8192      # 64 KiB of LDS / (16 B | 8 B) per entry of y
+    if mcyc > kd_max:
+        # xk_gmres_solve keeps the least-squares solution of a system in LDS: at most 8192 (complex: 4096) basis vectors
+        # per cycle (the dense Hessenberg of such a run is 8 S k^2 bytes long before that).  An explicit restart length
+        # beyond it is refused here; the un-restarted default (max_niter = None -> the operator's order, solve.py:389) only fails if
         # a run really gets that far — almost every run converges in a few dozen steps whatever the order
         if restart is not None:
-            raise NativeLibraryError("xitorch_amd gmres: restart=%d exceeds the supported cycle length (8192 basis "
-                                     "vectors per system)" % restart)
-        lazy_limit, mcyc = 8192, 8192
+            raise NativeLibraryError("xitorch_amd gmres: restart=%d exceeds the supported cycle length (%d basis "
+                                     "vectors per system)" % (restart, kd_max))
+        lazy_limit, mcyc = kd_max, kd_max
     rhs = prob.rhs.reshape(S, ld)
     beta = rhs.norm(dim=-1)                                                      # (S,)
     best = float(allreduce_max_(beta.max().double().reshape(1), process_group).item())      # solve.py:380-381
@@ -655,9 +663,16 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         x_base = None                         # restarted cycles: the iterate the current cycle corrects
         Q = torch.zeros((S, cap, ld), dtype=dtype, device=dev)
         Q[:, 0] = rhs / torch.where(beta == 0, torch.full_like(beta, eps), beta).unsqueeze(-1)   # :385, _safedenom
-        st = _GmresState(S, cap - 1, dev)
+        st = _GmresState(S, cap - 1, dev, cplx=prob.cplx)
         st.g[:, 0] = beta.double()
-        inv_hn = torch.zeros((S,), dtype=dtype, device=dev)
+        inv_hn = torch.zeros((S,), dtype=prob.rdtype, device=dev)
+        if prob.cplx:
+            # complex: the two Gram passes write into (S, cap + 1) coefficient rows; the fixed-shape reduction of
+            # xk_gmres_gram_c* wants one double pair per (system, tile, row) of scratch
+            gtiles = K.gmres_gram_tiles(N, dtype)
+            c1 = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
+            c2n = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
+            gscr = torch.zeros((S * gtiles * (cap + 1) * 2,), dtype=torch.float64, device=dev)
         Pest, Ptrue = kr.partial_real(), kr.partial_real()
         ycoef = torch.zeros((S, 1, cap), dtype=dtype, device=dev)
         status4 = torch.zeros((4,), dtype=torch.float64, device=dev)
@@ -673,7 +688,10 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
             check(fn("xk_gmres_solve_" + sfx)(ptr(st.R), ptr(st.g), ptr(ycoef), ycoef.stride(0), S, kd, st.cap,
                                               stream_ptr()), "xk_gmres_solve")
             x = xbufs[cur_i]
-            K.lincomb(Q, ycoef, x, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
+            if prob.cplx:
+                K.lincomb_c(Q, ycoef, x, kd, 1, alpha=1.0, beta=0.0, N=N)
+            else:
+                K.lincomb(Q, ycoef, x, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
             if x_base is not None:
                 x.add_(x_base)
             prob.apply(x.reshape(prob.Bt, prob.nc, ld), tmp)
@@ -695,6 +713,10 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                 Q, cap = Qn, newcap
                 ycoef = torch.zeros((S, 1, cap), dtype=dtype, device=dev)
                 st.grow(cap - 1, mcyc)
+                if prob.cplx:
+                    c1 = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
+                    c2n = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
+                    gscr = torch.zeros((S * gtiles * (cap + 1) * 2,), dtype=torch.float64, device=dev)
             # w = A q_j (solve.py:390) straight into basis row j+1; with a shift E the fused shift kernel wants
             # contiguous (S, ld) arrays, so q_j / w pass through two contiguous buffers (O(N) copies)
             if prob.E is None:
@@ -704,9 +726,14 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                 prob.apply(rtrue, tmp)
                 Q[:, j + 1].copy_(tmp.reshape(S, ld))
             wrow = Q[:, j + 1:j + 2]
-            c1 = K.dense_mm(Q[:, :j + 1, :N], wrow[:, :, :N])                      # (S, 1, j+1): <q_i, w>
-            K.lincomb(Q, c1, wrow, j + 1, 1, coef_layout="ca", alpha=-1.0, beta=1.0)
-            c2n = K.dense_mm(Q[:, :j + 2, :N], wrow[:, :, :N])                     # second pass; last entry |w1|^2
+            if prob.cplx:
+                K.gmres_gram_c(Q, Q[:, j + 1], c1, gscr, j + 1, N)                 # c1[s, i] = <q_i, w>, i <= j
+                K.lincomb_c(Q, c1.unsqueeze(1), wrow, j + 1, 1, alpha=-1.0, beta=1.0, N=N)
+                K.gmres_gram_c(Q, Q[:, j + 1], c2n, gscr, j + 1, N)                # second pass; entry j+1 = |w1|^2
+            else:
+                c1 = K.dense_mm(Q[:, :j + 1, :N], wrow[:, :, :N])                  # (S, 1, j+1): <q_i, w>
+                K.lincomb(Q, c1, wrow, j + 1, 1, coef_layout="ca", alpha=-1.0, beta=1.0)
+                c2n = K.dense_mm(Q[:, :j + 2, :N], wrow[:, :, :N])                 # second pass; last entry |w1|^2
             check(fn("xk_gmres_step_" + sfx)(ptr(c1), c1.stride(0), ptr(c2n), c2n.stride(0), j, st.cap, ptr(st.R),
                                              ptr(st.cs), ptr(st.sn), ptr(st.g), ptr(inv_hn), ptr(Pest), S,
                                              stream_ptr()), "xk_gmres_step")

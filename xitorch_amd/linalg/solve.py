@@ -3,7 +3,8 @@
 Same signature, defaults, argument checks and adjoint backward as the reference
 (xitorch/linalg/solve.py:13-243).  The iterative methods ("cg", "bicgstab", "gmres", "minres",
 "broyden1") are the native HIP implementations of xitorch_amd/linalg/native_krylov.py;
-"exactsolve" is the dense `torch.linalg.solve` path.
+"exactsolve" is the dense `torch.linalg.solve` path.  Every iterative method of `solve` serves real and complex
+operators ("gmres" included — an extension: the reference's gmres is real-only; "minres" needs a Hermitian one).
 """
 import warnings
 import torch
