@@ -21,7 +21,9 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 @pytest.mark.parametrize("trans", [False, True])
 def test_banded_mm_vs_oracle(dev, B, N, hb, C, dtype, trans):
     g = torch.Generator().manual_seed(N + hb)
-    band = torch.randn(B, 2 * hb + 1, N, dtype=dtype, generator=g)      # out-of-matrix entries hold garbage
+    band = torch.randn(B, 2 * hb + 1, N, dtype=dtype, generator=g)
+    col = torch.arange(N).unsqueeze(0) + torch.arange(2 * hb + 1).unsqueeze(1) - hb
+    band[:, (col < 0) | (col >= N)] = float("nan")                      # out-of-matrix entries: never to be used
     X = torch.randn(B, C, N, dtype=dtype, generator=g)
     op = oops.BandedOp(band.double())
     xo = X.double().transpose(-2, -1)

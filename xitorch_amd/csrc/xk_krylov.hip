@@ -721,9 +721,17 @@ static int banded_launch(const T* band, const T* Xc, T* Yc, int B, int N, int hb
 template <typename T>
 static int banded_mm(const T* band, const T* X, T* Y, int B, int N, int hb, int C, long sBand, long ldx,
                      long sX, long ldy, long sY, int trans, hipStream_t st) {
+  // columns per launch: 8, or as many as fit the 160 KiB of LDS next to a wide band's halo, so that whether a band
+  // is served does not depend on how many right-hand sides the caller batches; nothing is launched (and Y is not
+  // touched) when not even one column fits
+  constexpr size_t ROWS = 256 * Vec16<T>::n;
+  const size_t col_bytes = (ROWS + 2 * (size_t)hb) * sizeof(T);
+  const size_t fit = (size_t)(160 * 1024) / col_bytes;
+  if (fit < 1) return XK_ERR_UNSUPPORTED;
+  const int pcmax = fit < 8 ? (int)fit : 8;
   int c0 = 0;
   while (c0 < C) {
-    const int pc = (C - c0) >= 8 ? 8 : (C - c0);
+    const int pc = (C - c0) >= pcmax ? pcmax : (C - c0);
     const T* Xc = X + (long)c0 * ldx;
     T* Yc = Y + (long)c0 * ldy;
     int rc = XK_ERR_UNSUPPORTED;

@@ -425,22 +425,47 @@ def small_eigh(T, k, p, uppest=False, max_sweeps=16, method="jacobi", threads=0,
 
 
 # --------------------------------------------------------------------------- banded operator
+def _rows_disjoint(B, C, N, sB, ld):
+    """do the B * C rows of N elements of a (B, C, N) output at batch stride sB and row pitch ld occupy distinct
+    memory?  (either index may be the slower one; an index of extent 1 has no stride to speak of)"""
+    dims = sorted((s, n) for s, n in ((sB, B), (ld, C)) if n > 1)
+    span = N
+    for s, n in dims:
+        if s < span:
+            return False
+        span = (n - 1) * s + N
+    return True
+
+
 def banded_mm(band, X, out=None, trans=False):
     """Y[b,c,:] = A_b X[b,c,:] for DIA-stored banded operators: band (B or 1, 2*hb+1, N),
     band[b,d,i] = A_b[i, i+d-hb].  X, Y panel-major (B, C, N)."""
     require_device(band, "band")
     require_device(X, "panel")
+    ldx, sX = _panel_strides(X)
     B, C, N = X.shape
-    nd = band.shape[-2]
-    if band.shape[-1] != N or nd % 2 != 1:
+    if band.dim() not in (2, 3) or band.shape[-1] != N or band.shape[-2] % 2 != 1:
         raise _capi.NativeLibraryError("band shape %s does not match panel length %d" % (tuple(band.shape), N))
+    nd = band.shape[-2]
+    # the entry point reinterprets the band pointer by the panel's type and strides it by the panel's batch
+    if band.dtype != X.dtype or band.device != X.device:
+        raise _capi.NativeLibraryError("banded_mm: band is %s on %s, panel %s on %s"
+                                       % (band.dtype, band.device, X.dtype, X.device))
+    nb = band.shape[0] if band.dim() == 3 else 1
+    if nb != 1 and nb != B:
+        raise _capi.NativeLibraryError("banded_mm: band batch %d does not match panel batch %d" % (nb, B))
     if not band.is_contiguous():
         raise _capi.NativeLibraryError("band must be contiguous")
-    sBand = band.stride(0) if (band.dim() == 3 and band.shape[0] != 1) else 0
-    ldx, sX = _panel_strides(X)
+    sBand = nd * N if nb > 1 else 0             # one operator (a batch of 1 included) is broadcast over the panel batch
     if out is None:
         out = torch.empty((B, C, N), dtype=X.dtype, device=X.device)
+    elif out.shape != X.shape or out.dtype != X.dtype or out.device != X.device:
+        raise _capi.NativeLibraryError("banded_mm: out is %s %s on %s, expected %s %s on %s"
+                                       % (tuple(out.shape), out.dtype, out.device, (B, C, N), X.dtype, X.device))
     ldy, sY = _panel_strides(out)
+    if out.numel() > 0 and not _rows_disjoint(B, C, N, sY, ldy):
+        raise _capi.NativeLibraryError("banded_mm: rows of out overlap (shape %s, strides %s)"
+                                       % (tuple(out.shape), out.stride()))
     rc = fn("xk_banded_mm_" + suffix(X.dtype))(ptr(band), ptr(X), ptr(out), B, N, nd // 2, C, sBand, ldx, sX,
                                                 ldy, sY, 1 if trans else 0, stream_ptr())
     check(rc, "xk_banded_mm")
