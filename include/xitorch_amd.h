@@ -606,6 +606,34 @@ int xk_minres_update_c64(float* v, const float* y, float* w1, const float* w2, f
                          const float* Pbeta, int beta_is_dot, double* state, float* phi2, int S, int N, long ld,
                          int nblk, int k, void* stream);
 
+/* ---- Chebyshev filter step (extension: Zhou, Saad, Tiago, Chelikowsky 2006; symeig method "chebfsi") ----------
+ * Panels are (Bt, p, ld*) arrays: Bt operators, p vectors each, every vector a contiguous run of N elements; each of
+ * the four panels has its own pitch ld* >= N and batch stride s* >= 0 (elements; complex elements for _c128 / _c64,
+ * which address interleaved (re, im) storage).  For every b < Bt, c < p, n < N
+ *     out[b,c,n] = coef[3b] * AY[b,c,n] + coef[3b+1] * Y[b,c,n] + coef[3b+2] * Yprev[b,c,n]
+ * coef: (Bt, 3) DOUBLES on the device (alpha, beta, gamma per operator, real for every suffix), read by the kernel:
+ * no host synchronisation.  _f64 / _c128 evaluate in double; _f32 / _c64 round each coefficient once to float and
+ * evaluate in float; the sum is (alpha AY + beta Y) + gamma Yprev, products may be contracted into FMAs.
+ * gamma == 0.0 exactly (either sign): Yprev[b] is not read (it may hold NaN / Inf) — the first step of a filter.
+ * out may BE Yprev (same pointer, pitch and batch stride) or lie apart from it.  XK_ERR_ARG, nothing launched, nothing
+ * written: the address range of out intersects that of AY or Y (or that of a Yprev it is not identical to), N <= 0,
+ * Bt <= 0, p <= 0, a pitch below N, a negative stride, a NULL pointer, rows of out that overlap each other (Bt > 1 and
+ * sO < (p - 1) * ldO + N).  Only out[b, c, :N] is written (pads stay).
+ * Every base 16 B aligned and every pitch / batch stride a multiple of the 16 B vector: vector form (16 B non-temporal
+ * loads, 4 per lane and array in flight); any other layout: scalar form, same result contract.  4 Bt p N s bytes. */
+int xk_cheb_step_f64(const double* AY, long ldA, long sA, const double* Y, long ldY, long sY, const double* Yprev,
+                     long ldP, long sP, double* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
+                     void* stream);
+int xk_cheb_step_f32(const float* AY, long ldA, long sA, const float* Y, long ldY, long sY, const float* Yprev,
+                     long ldP, long sP, float* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
+                     void* stream);
+int xk_cheb_step_c128(const double* AY, long ldA, long sA, const double* Y, long ldY, long sY, const double* Yprev,
+                      long ldP, long sP, double* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
+                      void* stream);
+int xk_cheb_step_c64(const float* AY, long ldA, long sA, const float* Y, long ldY, long sY, const float* Yprev,
+                     long ldP, long sP, float* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
+                     void* stream);
+
 /* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
  * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
  * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.

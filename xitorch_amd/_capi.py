@@ -152,6 +152,8 @@ def _declare(L):
         sigs["xk_minres_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
         sigs["xk_minres_lanczos_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, I, P])
         sigs["xk_minres_update_" + sfx] = (I, [P] * 7 + [I, P, P, I, I, Lg, I, I, P])
+    for sfx in ("f64", "f32", "c128", "c64"):
+        sigs["xk_cheb_step_" + sfx] = (I, [P, Lg, Lg] * 4 + [P, I, I, I, P])
     sigs["xk_herm_eigh_lds_bytes"] = (Lg, [I, I, I])
     sigs["xk_herm_eigh_workspace_elems"] = (Lg, [I, I, I])
     for sfx in ("c128", "c64"):

@@ -668,6 +668,43 @@ def minres_update(v, y, w1, w2, x, Palpha, Pbeta, beta_is_dot, state, phi2, S, N
                                                     int(k), stream_ptr()), "xk_minres_update")
 
 
+# --------------------------------------------------------------------------- Chebyshev filter step (xk_cheb.hip)
+def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
+    """out[b,c,:N] = coef[b,0] * AY[b,c,:N] + coef[b,1] * Y[b,c,:N] + coef[b,2] * Yprev[b,c,:N]  (xk_cheb_step_*): the
+    three-term step of a Chebyshev filter on (Bt, p, ld) panels of one dtype (real or complex), unit stride along the
+    vector.  coef: (Bt, 3) float64 on the device, read by the kernel (no host synchronisation).  out: None = Yprev
+    itself (the driver's ring: the oldest panel is overwritten), or a panel apart from it; never AY or Y.  Where
+    coef[b,2] == 0 exactly, Yprev[b] is not read.  N: vector length (default: the panels' whole last dimension); only
+    out[:, :, :N] is written.  raw=True returns the status code instead of raising (tests of the argument checks)."""
+    if out is None:
+        out = Yprev
+    for t in (AY, Y, Yprev, out):
+        require_device(t, "panel")
+        if t.dim() != 3 or t.shape[:2] != AY.shape[:2] or t.dtype != AY.dtype or (t.shape[2] > 1 and t.stride(2) != 1):
+            raise _capi.NativeLibraryError("cheb_step: panels must be (Bt, p, ld) of one dtype and shape, unit stride "
+                                           "along the vector")
+    if AY.is_complex():
+        _require_resolved("cheb_step", AY, Y, Yprev, out)
+    Bt, p = AY.shape[0], AY.shape[1]
+    require_device(coef, "coefficients")
+    if coef.dtype != torch.float64 or coef.shape != (Bt, 3) or not coef.is_contiguous():
+        raise _capi.NativeLibraryError("cheb_step: coef must be a contiguous (Bt, 3) float64 tensor")
+    if N is None:
+        N = min(t.shape[2] for t in (AY, Y, Yprev, out))
+    elif any(t.shape[2] < N for t in (AY, Y, Yprev, out)) and N > 0:
+        raise _capi.NativeLibraryError("cheb_step: a panel is shorter than N = %d" % N)
+    args = []
+    for t in (AY, Y, Yprev, out):
+        # (a one-vector panel / a one-member batch may carry any stride there)
+        args += [ptr(t), t.stride(1) if (p > 1 or t.stride(1) >= t.shape[2]) else t.shape[2],
+                 t.stride(0) if Bt > 1 else 0]
+    rc = fn("xk_cheb_step_" + suffix(AY.dtype))(*args, ptr(coef), Bt, p, int(N), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_cheb_step")
+    return out
+
+
 # --------------------------------------------------------------------------- complex operators (real embedding)
 def _as_real_matrix(A):
     """zero-copy real view (.., M, 2N) of a complex matrix (.., M, N): row i = (Re A_i0, Im A_i0, Re A_i1, ...)"""

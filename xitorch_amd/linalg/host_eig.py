@@ -15,9 +15,9 @@ from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
 from xitorch_amd.dist import allreduce_max_
 
-__all__ = ["davidson"]
+__all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard"]
 
-calls = {"davidson": 0}
+calls = {"davidson": 0, "chebfsi": 0}
 
 
 def _H(x):
@@ -117,3 +117,209 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
         trace.update(niter=niter, napply=napply, resid_history=history, basis_size=int(V.shape[-1]),
                      best_resid=float(best_resid), groups=1, panel_kernel="host")
     return best
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Chebyshev-filtered subspace iteration (extension; Zhou, Saad, Tiago, Chelikowsky, J. Comput. Phys. 219 (2006) 172)
+# ---------------------------------------------------------------------------------------------------------------------
+def cheb_default_nguard(neig, N):
+    """guard vectors of the filtered block: max(8, ceil(neig / 4)), capped so that neig + nguard <= N"""
+    return max(0, min(max(8, -(-neig // 4)), N - neig))
+
+
+def cheb_coefficients(a, b, a0, degree, sign=1.0):
+    """Coefficient table of one scaled Chebyshev filter: (degree, *S, 3) float64 from the float64 tensors a, b, a0 of
+    shape S (any device; a handful of elementwise ops, no host synchronisation).  The filter is for B = sign * A with
+    the unwanted part of B's spectrum in [a, b] and the scaling point a0 < a; step i computes
+        Y_i = alpha_i (A Y_{i-1}) + beta_i Y_{i-1} + gamma_i Y_{i-2},     (alpha, beta, gamma) = table[i - 1]
+    so that Y_m = p_m(B) Y_0 with p_m(t) = T_m((t - c) / e) / T_m((a0 - c) / e), c = (a + b) / 2, e = (b - a) / 2:
+    sigma_1 = e / (a0 - c), Y_1 = (sigma_1 / e)(B - c) Y_0, then sigma' = 1 / (2 / sigma_1 - sigma),
+    Y_i = (2 sigma' / e)(B - c) Y_{i-1} - sigma sigma' Y_{i-2}.  `sign` enters alpha only (B Y = sign * A Y).
+    An interval without width (a zero operator, a multiple of the identity) gets the identity filter (0, 1, 0)."""
+    a, b, a0 = a.to(torch.float64), b.to(torch.float64), a0.to(torch.float64)
+    width = b - a0
+    flat = ~(width > 1e-14 * torch.maximum(b.abs(), a0.abs()))          # (also NaN)
+    safe_w = torch.where(flat, torch.ones_like(width), width)
+    # keep the cut strictly inside (a0, b): a block whose Ritz values coincide must not collapse the interval
+    a = torch.minimum(torch.maximum(a, a0 + 1e-3 * safe_w), b - 1e-3 * safe_w)
+    a = torch.where(flat, a0 - 1.0, a)
+    b = torch.where(flat, a0 + 1.0, b)
+    e = (b - a) * 0.5
+    c = (b + a) * 0.5
+    sigma1 = e / (a0 - c)
+    sigma = sigma1
+    one, zero = torch.ones_like(e), torch.zeros_like(e)
+    rows = []
+    for i in range(degree):
+        if i == 0:
+            al, be, ga = sigma1 / e, -c * sigma1 / e, zero
+        else:
+            sn = 1.0 / (2.0 / sigma1 - sigma)
+            al, be, ga = 2.0 * sn / e, -2.0 * sn * c / e, -sigma * sn
+            sigma = sn
+        al, be, ga = torch.where(flat, zero, al * sign), torch.where(flat, one, be), torch.where(flat, zero, ga)
+        rows.append(torch.stack((al, be, ga), dim=-1))
+    return torch.stack(rows, dim=0)
+
+
+def _cheb_check_args(name, M, process_group):
+    if M is not None:
+        raise NotImplementedError("%s: an overlap operator M is not supported: the Chebyshev filter of A X = M X E acts "
+                                  "on M^-1 A, and no M^-1 is available here; use method='davidson'" % name)
+    if process_group is not None:
+        raise NotImplementedError("%s: batch sharding over a process group is not supported by the filtered subspace "
+                                  "iteration; use method='davidson'" % name)
+
+
+def _cheb_lanczos_vector(bdims, N, dtype):
+    """the one start vector of the bound-estimating Lanczos run: drawn on the host from a generator of its own (the
+    global generators are left alone), the same numbers for the host twin and the device driver"""
+    g = torch.Generator().manual_seed(12421 + 1)
+    rd = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    v = torch.randn((*bdims, N, 1), dtype=rd, generator=g)
+    return v.to(dtype)
+
+
+def _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device):
+    """(B, w, N) panel-major start block: `_initial_block`'s, a caller's V0 completed by random columns when it has
+    fewer than w"""
+    from xitorch_amd.linalg.native_eig import _initial_block
+    if V0 is None:
+        return _initial_block(v_init, None, bdims, B, N, w, dtype, dev, rng_device)
+    V = _initial_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device)
+    k = V.shape[1]
+    if k >= w:
+        return V[:, :w]
+    extra = _initial_block("randn", None, bdims, B, N, w - k, dtype, dev, rng_device)
+    return torch.cat((V, extra), dim=1)
+
+
+def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguard=None, V0=None, v_init="randn",
+            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, **unused):
+    """Chebyshev-filtered subspace iteration in torch ops for a Hermitian operator in HOST memory: the statement of
+    `native_chebfsi.chebfsi` (same options, same refusals, same decisions).  A block of w = neig + nguard vectors; per
+    outer iteration `degree` applies through the three-term filter step, two orthonormalisation passes, one apply and a
+    Rayleigh-Ritz of order w; the cut of the filter follows the block's largest Ritz value.  mode="uppest" filters -A
+    through the sign of the coefficients.  A block that fails the guard is redone from the pre-filter block with a third
+    pass and half the degree, which stay in force for the rest of the run; a second failure raises.  Stopping rule, best-block return and the guard thresholds are davidson's."""
+    import warnings
+    from xitorch_amd._util import ConvergenceWarning
+    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD
+    calls["chebfsi"] += 1
+    _cheb_check_args("chebfsi", M, process_group)
+    dev = torch.device(A.device)
+    if dev.type != "cpu":
+        raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "
+                                 "run on the HIP kernels" % dev)
+    N, dtype = A.shape[-1], A.dtype
+    bdims = list(A.shape[:-2])
+    B = 1
+    for d in bdims:
+        B *= d
+    if nguard is None:
+        nguard = cheb_default_nguard(neig, N)
+    w = min(N, neig + int(nguard))
+    if V0 is not None and w < V0.shape[-1]:
+        w = min(N, V0.shape[-1])
+    if N <= max(2 * w, 16):
+        if trace is not None:
+            trace.update(niter=0, napply=0, degree=degree, w=w, handed_to="exacteig")
+        return exacteig(A, neig, mode, None)
+    sign = 1.0 if mode == "lowest" else -1.0
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    napply = 0
+
+    def apply(X):
+        nonlocal napply
+        napply += 1
+        return A.mm(X)
+
+    def orth(Y, passes):
+        for _ in range(passes):
+            Y, _R = torch.linalg.qr(Y)
+        return Y
+
+    X = _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device)          # (B, w, N)
+    X = orth(X.transpose(-2, -1).reshape(*bdims, N, w), 2)
+
+    # spectral bounds of B = sign * A from a short Lanczos run (Zhou & Li's safeguarded upper bound)
+    ks = max(2, min(int(lanczos_steps), N - 1))
+    v = _cheb_lanczos_vector(bdims, N, dtype)
+    v = v / torch.linalg.vector_norm(v, dim=-2, keepdim=True)
+    vprev = torch.zeros_like(v)
+    Tl = torch.zeros((*bdims, ks, ks), dtype=torch.float64)
+    beta = torch.zeros((*bdims,), dtype=torch.float64)
+    for j in range(ks):
+        f = apply(v)
+        al = (v.conj() * f).sum(dim=(-2, -1)).real.to(torch.float64)
+        f = f - al.to(rdt)[..., None, None] * v - beta.to(rdt)[..., None, None] * vprev
+        Tl[..., j, j] = al
+        beta = torch.linalg.vector_norm(f, dim=(-2, -1)).to(torch.float64)
+        if j + 1 < ks:
+            Tl[..., j, j + 1] = beta
+            Tl[..., j + 1, j] = beta
+            inv = torch.where(beta > 0, 1.0 / beta, torch.zeros_like(beta))
+            vprev, v = v, f * inv.to(rdt)[..., None, None]
+    theta = torch.linalg.eigvalsh(Tl) * sign                                           # Ritz values of B
+    th_min, th_max = theta.min(dim=-1)[0], theta.max(dim=-1)[0]
+    b_sup = th_max + beta
+    a0 = th_min
+    a = theta.median(dim=-1)[0]
+
+    gbad = GUARD_BAD[rdt]
+    best_resid, best = float("inf"), None
+    history, redo = [], []
+    niter, deg_now, passes = 0, int(degree), 2
+    eye = torch.eye(w, dtype=dtype)
+    for it in range(max_niter):
+        niter = it + 1
+        while True:
+            coef = cheb_coefficients(a, b_sup, a0, deg_now, sign).to(rdt)              # (deg, *bdims, 3)
+            Yp, Y = None, X
+            for i in range(deg_now):
+                AY = apply(Y)
+                c3 = coef[i][..., None, None, :]
+                Yn = c3[..., 0] * AY + c3[..., 1] * Y
+                if i > 0:
+                    Yn = Yn + c3[..., 2] * Yp
+                Yp, Y = Y, Yn
+            Q = orth(Y, passes)
+            AQ = apply(Q)
+            T = torch.matmul(_H(Q), AQ)
+            mu, Yr = torch.linalg.eigh((T + _H(T)) * (0.5 * sign))
+            Xn = torch.matmul(Q, Yr)
+            lam = mu * sign
+            R = torch.matmul(AQ, Yr[..., :neig]) - Xn[..., :neig] * lam[..., None, :neig]
+            guard = float((torch.matmul(_H(Xn), Xn) - eye).abs().max())
+            max_resid = float(R.abs().max())
+            if guard <= gbad:
+                break
+            redo.append({"iter": niter, "guard": guard, "passes": passes + 1, "degree": max(1, deg_now // 2)})
+            if len(redo) > 1:
+                raise RuntimeError("xitorch_amd chebfsi: the filtered block lost its orthonormality twice (max|X^H X - "
+                                   "I| = %.2e at iteration %d)" % (guard, niter))
+            passes, deg_now = 3, max(1, deg_now // 2)
+        X = Xn
+        if max_resid != max_resid:
+            max_resid = float("inf")
+        history.append(max_resid)
+        if verbose:
+            print("Iter %3d (block of %d, degree %d): resid: %.3e" % (niter, w, deg_now, max_resid))
+        if max_resid < best_resid:
+            best_resid, best = max_resid, (lam[..., :neig], Xn[..., :neig])
+        if max_resid < min_eps:
+            break
+        a, a0 = mu.max(dim=-1)[0].to(torch.float64), mu.min(dim=-1)[0].to(torch.float64)
+    if best is None:
+        raise RuntimeError("xitorch_amd chebfsi: no finite residual was produced")
+    if not best_resid < min_eps:
+        warnings.warn(ConvergenceWarning("chebfsi: convergence is not achieved after %d iterations (max |resid| = %.3e "
+                                         ">= min_eps = %.3e); the best block is returned" % (niter, best_resid, min_eps)))
+    if trace is not None:
+        trace.update(niter=niter, napply=napply, degree=deg_now, w=w, resid_history=history, best_resid=best_resid,
+                     bounds={"a": a.tolist(), "b_sup": b_sup.tolist(), "a0": a0.tolist()}, small_eigh="library",
+                     guard_redo=redo, panel_kernel="host")
+    evals, evecs = best
+    if mode != "lowest":
+        evals, evecs = evals.flip(-1), evecs.flip(-1)
+    return evals, evecs

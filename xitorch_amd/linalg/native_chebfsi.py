@@ -1,0 +1,377 @@
+"""Chebyshev-filtered subspace iteration on the HIP kernels: `symeig(..., method="chebfsi")`.
+
+An extension (the reference has no counterpart; Zhou, Saad, Tiago, Chelikowsky, J. Comput. Phys. 219 (2006) 172).
+Block Davidson grows a basis and repeats a Rayleigh-Ritz over all of it every iteration; for MANY pairs of a large
+operator that chain becomes the cost.  Here the block has a fixed width w = neig + nguard and an outer iteration is
+
+  1. `degree` times: one operator-panel product on the whole block (`PanelOperator.apply`: the wide panel kernels) and
+     one `xk_cheb_step` — the only pass over the block between two applies — on a ring of panels; the coefficient table
+     of the whole filter is a handful of torch ops on (Bt,) device tensors, no step synchronises with the host;
+  2. two passes of CholeskyQR on the filtered block (`xk_davidson_orth`; complex: `xk_herm_cholqr` in chunks of 32);
+  3. one more apply, the Gram block Q^H A Q on K1, the native dense eigensolver on it (`native_partial_eigh`; complex:
+     `xk_herm_eigh` up to 32 vectors, the library beyond), the rotation (`xk_ritz_residual` for the wanted columns, `xk_lincomb` for the guard columns), the
+     a-posteriori guard max|X^H X - I| (`xk_ritz_guard`) and ONE host read of {max|resid|, Cholesky flag, guard} — plus
+     the read of the dense eigensolver's self-check flags inside `native_partial_eigh` / `herm_partial_eigh` (one per
+     call: one for real blocks and complex blocks up to 16 vectors, two and a seam test for complex blocks of 17 .. 32).
+
+Storage: the Ritz block, the two ring panels, the product panel, the best block seen and a residual panel.  The spectral bounds come from
+a short Lanczos run on the device (`xk_kry_dots` + `xk_cheb_step` as its three-term update).  `host_eig.chebfsi` is the
+same algorithm in torch ops for operators in host memory.  Not built: an overlap operator M, batch sharding, locking of
+converged columns.
+"""
+import warnings
+import torch
+from xitorch_amd import kernels as K
+from xitorch_amd._capi import NativeLibraryError, fn, ptr, check, suffix, stream_ptr
+from xitorch_amd._util import ConvergenceWarning
+from xitorch_amd.linalg._panel import PanelOperator, pad_len
+from xitorch_amd.linalg import host_eig
+from xitorch_amd.linalg.host_eig import cheb_coefficients, cheb_default_nguard
+
+__all__ = ["chebfsi"]
+
+
+class _RealBlock:
+    """fp64 / fp32 blocks: zero-padded (Bt, w, pad_len(N)) panels on the Davidson chain kernels"""
+
+    def __init__(self, Bt, N, w, neig, dtype, device):
+        from xitorch_amd.linalg.native_eig import EXACTEIG_NATIVE_MAX_P
+        self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
+        self.ld = pad_len(N)
+        q = max(w, 32)
+        self.C = torch.empty((Bt * q * q,), dtype=dtype, device=device)
+        self.W = torch.empty((Bt * 32 * 32,), dtype=dtype, device=device)
+        self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
+        self.rmax = torch.zeros((Bt,), dtype=dtype, device=device)
+        self.orth_g = torch.zeros((Bt,), dtype=dtype, device=device)
+        self.status = torch.zeros((5,), dtype=torch.float64, device=device)
+        self.native = (8 <= w <= EXACTEIG_NATIVE_MAX_P and K.small_eigh_big_ok(w, w, dtype)) or \
+            (w < 8 and w <= K.SMALL_EIGH_MAX_P)
+        self.small_eigh = "native" if self.native else "library"
+
+    def panel(self):
+        return torch.zeros((self.Bt, self.w, self.ld), dtype=self.dtype, device=self.device)
+
+    def load(self, P, V0p):
+        P[:, :, :self.N].copy_(V0p)
+
+    def orth(self, P, passes):
+        self.info.zero_()
+        K.davidson_orth(P, self.N, 0, self.w, self.C, self.W, self.info, passes=passes)
+
+    def rayleigh_ritz(self, Q, AQ, X, scratch, sign):
+        """X <- the Ritz block of span(Q) ordered by sign * lambda ascending; returns (lam (Bt, w) true eigenvalues in
+        that order, mu = sign * lam (ascending), [max|resid| over the wanted columns, Cholesky flag, guard])"""
+        from xitorch_amd.linalg.native_eig import native_partial_eigh
+        N, w, neig = self.N, self.w, self.neig
+        G = K.dense_mm(Q[:, :, :N], AQ[:, :, :N])                        # G[b, c, a] = <Q_a, (A Q)_c>
+        T = ((G + G.transpose(1, 2)) * (0.5 * sign)).contiguous()
+        if self.native and w >= 8:
+            mu, Y = native_partial_eigh(T, w, "lowest")                 # (Bt, w), (Bt, w, w) = [basis index, pair]
+        elif self.native:
+            mu, Yt, _ = K.small_eigh(T, w, w)                            # LDS Jacobi kernel (tiny blocks)
+            Y = Yt.transpose(1, 2)
+        else:
+            mu, Y = torch.linalg.eigh(T)                                 # beyond the native dense eigensolver's widths
+        lam = (mu * sign).contiguous()
+        self.rmax.zero_()
+        K.ritz_residual(Q, AQ, Y, lam, X, scratch, self.rmax, w, neig)
+        if w > neig:
+            K.lincomb(Q, Y[:, :, neig:], X[:, neig:], w, w - neig, coef_layout="ac", alpha=1.0, beta=0.0)
+        K.ritz_guard(X, self.orth_g, w, self.ld)
+        K.group_status(self.rmax, self.info, None, self.status, orth=self.orth_g)
+        st = self.status.tolist()                                        # the one host read of the outer iteration
+        return lam, mu, (st[0], st[1], st[4])
+
+    def result(self, X, bdims):
+        return X[:, :self.neig, :self.N].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
+
+
+class _ComplexBlock:
+    """complex128 / complex64 blocks of any width: (Bt, w, N) panels on the Hermitian Davidson kernels (xk_herm_*)"""
+
+    def __init__(self, Bt, N, w, neig, dtype, device):
+        self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
+        self.ld = N
+        self.rdtype = torch.float64 if dtype == torch.complex128 else torch.float32
+        self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
+        self.status = torch.zeros((Bt + 1,), dtype=torch.float64, device=device)
+        self.counts = {"rr_native": 0, "rr_library": 0}
+        # xk_herm_eigh returns up to 16 pairs from either end of the spectrum: blocks of up to 32 vectors get all their
+        # pairs from two native calls (the lowest 16 and the uppermost w - 16); wider ones go to the library
+        self.native = w <= 2 * K.HERM_EIGH_MAX_P and w <= K.HERM_EIGH_MAX_K
+        self.small_eigh = "native" if self.native else "library"
+        self.eye = torch.eye(w, dtype=dtype, device=device)
+
+    def panel(self):
+        return torch.zeros((self.Bt, self.w, self.N), dtype=self.dtype, device=self.device)
+
+    def load(self, P, V0p):
+        P.copy_(V0p)
+
+    def orth(self, P, passes):
+        """CholeskyQR of the block with `passes` passes (the first shifted when there are several).  Blocks wider than
+        the 32 vectors of xk_herm_cholqr are taken 32 rows at a time, like xk_davidson_orth takes real ones: every chunk
+        is projected against the chunks before it (K1 Gram + K1 combination) and orthonormalised among itself, at
+        least twice — block Gram-Schmidt with CholeskyQR inside the blocks."""
+        from xitorch_amd.linalg.native_eig_herm import _shift_rel, _gram, _combine
+        self.info.zero_()
+        Q = K.HERM_CHOLQR_MAX_Q
+        for off in range(0, self.w, Q):
+            qc = min(Q, self.w - off)
+            chunk = P[:, off:off + qc]
+            np_ = max(1, passes) if off == 0 else max(2, passes)
+            for r in range(np_):
+                if off > 0:
+                    chunk.sub_(_combine(P[:, :off], _gram(P[:, :off], chunk)))
+                K.herm_cholqr(chunk, self.info, shift_rel=_shift_rel(self.N, qc, self.rdtype) if (r == 0 and np_ > 1)
+                              else 0.0)
+
+    def _eigh_all(self, T):
+        """all w eigenpairs of the Hermitian (Bt, w, w) T, ascending: (mu (Bt, w), Y (Bt, w, w) = [index, pair])"""
+        from xitorch_amd.linalg.native_eig_herm import herm_partial_eigh
+        w, P16 = self.w, K.HERM_EIGH_MAX_P
+        if not self.native:
+            self.counts["rr_library"] += 1
+            return torch.linalg.eigh(T)
+        if w <= P16:
+            return herm_partial_eigh(T, w, w, "lowest", self.counts)
+        mu_lo, Y_lo = herm_partial_eigh(T, w, P16, "lowest", self.counts)
+        mu_hi, Y_hi = herm_partial_eigh(T, w, w - P16, "uppest", self.counts)
+        # The seam.  xk_herm_eigh orthogonalises its vectors only within one call: vector 16 and vector 17 come out
+        # orthogonal to about eps |T| / gap.  Where that could reach the guard's GOOD level — eigenvalues 16 and 17 of
+        # some member closer than eps |T| / GUARD_GOOD — the call is served by the library, whose vectors are orthonormal
+        # whatever the gaps (one more host read, only for blocks of 17 .. 32 vectors).  Otherwise what is left across
+        # the seam is removed by one projection of the upper set against the lower and a renormalisation, a
+        # perturbation of the upper vectors below GUARD_GOOD.
+        from xitorch_amd.linalg.native_eig import GUARD_GOOD
+        scale = torch.maximum(mu_lo[:, 0].abs(), mu_hi[:, -1].abs())
+        tol = torch.finfo(self.rdtype).eps / GUARD_GOOD[self.rdtype]
+        if bool(((mu_hi[:, 0] - mu_lo[:, -1]) <= tol * scale).any()):
+            self.counts["rr_library"] += 1
+            return torch.linalg.eigh(T)
+        Y_hi = Y_hi - torch.matmul(Y_lo, torch.matmul(Y_lo.transpose(1, 2).conj(), Y_hi))
+        Y_hi = Y_hi / torch.linalg.vector_norm(Y_hi, dim=1, keepdim=True)
+        return torch.cat((mu_lo, mu_hi), dim=-1), torch.cat((Y_lo, Y_hi), dim=-1)
+
+    def rayleigh_ritz(self, Q, AQ, X, scratch, sign):
+        from xitorch_amd.linalg.native_eig_herm import _gram, _combine
+        w, neig = self.w, self.neig
+        T = _gram(Q, AQ)                                                  # T[b, i, c] = <Q_i, (A Q)_c>
+        T = ((T + T.transpose(1, 2).conj()) * (0.5 * sign)).contiguous()
+        mu, Y = self._eigh_all(T)
+        if self.counts["rr_library"]:
+            self.small_eigh = "library"
+        lam = (mu * sign).contiguous()
+        K.herm_ritz(Q, AQ, Y, lam, X, scratch, self.status, w, neig)
+        if w > neig:
+            X[:, neig:].copy_(_combine(Q, Y[:, :, neig:].contiguous()))
+        guard = (_gram(X, X) - self.eye).abs().max().to(torch.float64)
+        st = torch.stack((self.status[0], self.info.max().to(torch.float64), guard)).tolist()
+        return lam, mu, (st[0], st[1], st[2])
+
+    def result(self, X, bdims):
+        return X[:, :self.neig].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
+
+
+def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
+    """Ritz values and residual norm of a `steps`-step Lanczos run from one random vector per operator, all on the
+    device: apply, xk_kry_dots for <v, A v> and |f|^2, xk_cheb_step for f = A v - alpha v - beta v_prev and for the
+    normalisation.  Returns (theta (Bt, steps) of sign * A ascending, |f_k| (Bt,)) as float64 device tensors."""
+    cplx = dtype.is_complex
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    ld = pad_len(N)
+    vn = {torch.float64: 2, torch.float32: 4, torch.complex128: 1, torch.complex64: 2}[dtype]
+    nblk = max(1, min(fn("xk_kry_max_partials")(), (N + 256 * vn * 4 - 1) // (256 * vn * 4)))
+    dots_fn = fn("xk_kry_dots_" + suffix(dtype))
+    extra = (0,) if cplx else ()
+
+    def dot(x, y):
+        P = torch.zeros((Bt, 64, 2) if cplx else (Bt, 64), dtype=rdt, device=device)
+        check(dots_fn(ptr(x), ptr(y), ptr(None), ptr(None), ptr(None), ptr(None), ptr(P), ptr(None), Bt, N, ld, nblk,
+                      *extra, stream_ptr()), "xk_kry_dots")
+        P = P[:, :nblk, 0] if cplx else P[:, :nblk]
+        return P.to(torch.float64).sum(dim=1)
+
+    bufs = [torch.zeros((Bt, 1, ld), dtype=dtype, device=device) for _ in range(3)]
+    v0 = host_eig._cheb_lanczos_vector(bdims, N, dtype).reshape(Bt, N).to(device)
+    v0 = v0 / torch.linalg.vector_norm(v0, dim=-1, keepdim=True)
+    bufs[0][:, 0, :N].copy_(v0)
+    v, vprev, av = bufs
+    zero = torch.zeros((Bt,), dtype=torch.float64, device=device)
+    one = torch.ones_like(zero)
+    beta = zero
+    alphas, betas = [], []
+    for j in range(steps):
+        op.apply(v, av)
+        al = dot(v, av)
+        K.cheb_step(av, v, vprev, torch.stack((one, -al, -beta), dim=-1).contiguous(), N=N)     # f, over v_prev
+        f = vprev
+        beta = torch.sqrt(torch.clamp(dot(f, f), min=0.0))
+        alphas.append(al)
+        if j + 1 < steps:
+            betas.append(beta)
+            inv = torch.where(beta > 0, 1.0 / beta, zero)
+            K.cheb_step(v, f, av, torch.stack((zero, inv, zero), dim=-1).contiguous(), N=N)      # f / beta, over A v
+            v, vprev, av = av, v, f
+    Tl = torch.diag_embed(torch.stack(alphas, dim=-1))
+    if betas:
+        off = torch.stack(betas, dim=-1)
+        Tl = Tl + torch.diag_embed(off, offset=1) + torch.diag_embed(off, offset=-1)
+    Tl = (Tl * sign).contiguous()
+    if steps <= K.SMALL_EIGH_MAX_P:
+        theta, _, _ = K.small_eigh(Tl, steps, steps)
+    else:
+        from xitorch_amd.linalg.native_eig import native_partial_eigh
+        theta, _ = native_partial_eigh(Tl, steps, "lowest")
+    return theta, beta
+
+
+def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguard=None, V0=None, v_init="randn",
+            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, **unused):
+    """
+    Chebyshev-filtered subspace iteration for the ``neig`` lowest / uppermost eigenpairs of a large Hermitian operator
+    (dense, banded, CSR or a user ``_mv``; float64, float32, complex128, complex64; any batch shape), on the HIP kernels.
+    Meant for MANY pairs (32 .. 256), where block Davidson's Rayleigh-Ritz chain over a growing basis is the cost.
+
+    Keyword arguments
+    -----------------
+    max_niter: int
+        Maximum number of outer iterations (each: ``degree + 1`` operator applies on the whole block)
+    min_eps: float
+        Stop when the largest residual element ``max|A X - X diag(lam)|`` over the wanted columns of all operators is
+        below this (davidson's rule); otherwise the best block seen is returned with a ``ConvergenceWarning``
+    degree: int
+        Degree of the Chebyshev filter
+    nguard: int or None
+        Guard vectors: the block has ``neig + nguard`` columns.  Default ``max(8, ceil(neig / 4))``, capped at the order
+    V0: tensor or None
+        Start block ``(*batch, na, k)``; completed by random columns when ``k < neig + nguard``
+    v_init, rng_device: str
+        The start block, as for ``davidson`` (seed 12421)
+    lanczos_steps: int
+        Steps of the Lanczos run that estimates the spectral bounds (upper bound ``theta_max + |f_k|``)
+    trace: dict or None
+        Receives ``niter``, ``napply``, ``degree``, ``w``, ``bounds``, ``small_eigh`` (``"native"`` / ``"library"``),
+        ``guard_redo``, ``panel_kernel``, ``resid_history``
+
+    ``M`` and ``process_group`` raise ``NotImplementedError``.  ``mode="uppest"`` filters ``-A`` by negating the
+    coefficients.  A block wide enough to span (half of) the space is handed to ``exacteig``.  A block that fails the
+    a-posteriori guard ``max|X^H X - I| > GUARD_BAD`` is redone from the pre-filter block with a third orthonormalisation
+    pass and half the degree, and both stay in force for the rest of the run (a block that lost its orthonormality once
+    is not given the longer filter again); a second failure raises.
+    """
+    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD
+    device = torch.device(A.device)
+    if device.type == "cpu":
+        # device dispatch (see native_eig.davidson): an operator in HOST memory is served by host_eig.py
+        return host_eig.chebfsi(A, neig, mode, M, max_niter=max_niter, min_eps=min_eps, degree=degree, nguard=nguard,
+                                V0=V0, v_init=v_init, rng_device=rng_device, lanczos_steps=lanczos_steps,
+                                verbose=verbose, trace=trace, process_group=process_group)
+    host_eig._cheb_check_args("chebfsi", M, process_group)
+    if device.type != "cuda":
+        raise NativeLibraryError("xitorch_amd chebfsi runs on a HIP device only (operator is on %s)" % device)
+    dtype = A.dtype
+    if dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
+        raise NativeLibraryError("xitorch_amd chebfsi supports float64/float32 and complex128/complex64 operators, "
+                                 "got %s" % dtype)
+    N = A.shape[-1]
+    bdims = list(A.shape[:-2])
+    Bt = 1
+    for d in bdims:
+        Bt *= d
+    if nguard is None:
+        nguard = cheb_default_nguard(neig, N)
+    w = min(N, neig + int(nguard))
+    if V0 is not None and w < V0.shape[-1]:
+        w = min(N, V0.shape[-1])
+    if N <= max(2 * w, 16):
+        if trace is not None:
+            trace.update(niter=0, napply=0, degree=degree, w=w, handed_to="exacteig")
+        return exacteig(A, neig, mode, None)
+    sign = 1.0 if mode == "lowest" else -1.0
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    blk = (_ComplexBlock if dtype.is_complex else _RealBlock)(Bt, N, w, neig, dtype, device)
+    op = PanelOperator(A, bdims, Bt, N)
+    if trace is not None and trace.get("k1_events") is not None:
+        op.events = trace["k1_events"]
+
+    X, R0, R1, AY = blk.panel(), blk.panel(), blk.panel(), blk.panel()
+    best_X = blk.panel()
+    Tn = blk.panel()[:, :neig]                       # residual panel xk_ritz_residual writes beside the wanted columns
+    blk.load(X, host_eig._cheb_start_block(v_init, V0, bdims, Bt, N, w, dtype, device, rng_device))
+    blk.orth(X, 2)
+    if int(blk.info.max().item()) != 0:
+        raise RuntimeError("chebfsi: the start block is rank deficient (linearly dependent start vectors)")
+
+    ks = max(2, min(int(lanczos_steps), N - 1))
+    theta, fnorm = _lanczos_bounds(op, Bt, N, dtype, device, bdims, ks, sign)
+    b_sup = theta.max(dim=-1)[0].to(torch.float64) + fnorm
+    a0 = theta.min(dim=-1)[0].to(torch.float64)
+    a = theta.to(torch.float64).median(dim=-1)[0]
+
+    gbad = GUARD_BAD[rdt]
+    best_resid, best_lam = float("inf"), None
+    history, redo = [], []
+    niter, deg_now, passes = 0, int(degree), 2
+    for it in range(max_niter):
+        niter = it + 1
+        while True:
+            coef = cheb_coefficients(a, b_sup, a0, deg_now, sign).contiguous()           # (degree, Bt, 3) on the device
+            # ring: Y_{i-2} is overwritten by Y_i; the pre-filter block X is kept (a guard failure restarts from it)
+            Yp, Y, free = X, X, [R0, R1]
+            for i in range(deg_now):
+                op.apply(Y, AY)
+                if i == 0:
+                    out = free.pop()
+                    K.cheb_step(AY, Y, out, coef[0], out=out, N=N)                       # gamma = 0: out is not read
+                elif i == 1:
+                    out = free.pop()
+                    K.cheb_step(AY, Y, Yp, coef[1], out=out, N=N)
+                else:
+                    out = Yp
+                    K.cheb_step(AY, Y, Yp, coef[i], N=N)
+                Yp, Y = Y, out
+            Q = Y
+            other = R1 if Q is R0 else R0                                                # Y_{m-1} (dead) or unused
+            blk.orth(Q, passes)
+            op.apply(Q, AY)
+            lam, mu, (max_resid, chol_flag, guard) = blk.rayleigh_ritz(Q, AY, other, Tn, sign)
+            if guard != guard:
+                guard = float("inf")
+            if chol_flag == 0 and guard <= gbad:
+                break
+            redo.append({"iter": niter, "guard": guard, "chol_flag": chol_flag, "passes": 3,
+                         "degree": max(1, deg_now // 2)})
+            if len(redo) > 1:
+                raise RuntimeError("xitorch_amd chebfsi: the filtered block lost its orthonormality twice (max|X^H X - "
+                                   "I| = %.2e, Cholesky flag %d, at iteration %d)" % (guard, int(chol_flag), niter))
+            passes, deg_now = 3, max(1, deg_now // 2)
+        # the new Ritz block lives in `other`: it becomes X; the old X and Q are the ring of the next filter
+        X, R0, R1 = other, X, Q
+        if max_resid != max_resid:
+            max_resid = float("inf")
+        history.append(max_resid)
+        if verbose:
+            print("Iter %3d (block of %d, degree %d): resid: %.3e" % (niter, w, deg_now, max_resid))
+        if max_resid < best_resid:
+            best_resid, best_lam = max_resid, lam[:, :neig]
+            best_X.copy_(X)
+        if max_resid < min_eps:
+            break
+        a, a0 = mu.max(dim=-1)[0].to(torch.float64), mu.min(dim=-1)[0].to(torch.float64)
+    if best_lam is None:
+        raise RuntimeError("xitorch_amd chebfsi: no finite residual was produced")
+    if not best_resid < min_eps:
+        warnings.warn(ConvergenceWarning("chebfsi: convergence is not achieved after %d iterations (max |resid| = %.3e "
+                                         ">= min_eps = %.3e); the best block is returned" % (niter, best_resid, min_eps)))
+    if trace is not None:
+        trace.update(niter=niter, napply=op.napply, degree=deg_now, w=w, resid_history=history, best_resid=best_resid,
+                     bounds={"a": a.tolist(), "b_sup": b_sup.tolist(), "a0": a0.tolist()},
+                     small_eigh=blk.small_eigh, guard_redo=redo,
+                     panel_kernel=op.last_kernel if op.kind != "generic" else "generic")
+    evals = best_lam.reshape(*bdims, neig)
+    evecs = blk.result(best_X, bdims)
+    if mode != "lowest":
+        evals, evecs = evals.flip(-1), evecs.flip(-1)
+    return evals, evecs

@@ -10,6 +10,7 @@ import torch
 from xitorch_amd.linop import LinearOperator  # noqa: F401  (re-exported for type references in user code)
 from xitorch_amd.linalg.solve import solve
 from xitorch_amd.linalg.native_eig import davidson, exacteig
+from xitorch_amd.linalg.native_chebfsi import chebfsi
 from xitorch_amd.debug import is_debug_enabled
 from xitorch_amd._util import assert_runtime, merge_options, null_context, get_method, pop_keys, MathWarning
 
@@ -44,7 +45,9 @@ def symeig(A, neig=None, mode="lowest", M=None, bck_options={}, method=None, **f
         (thresholds below which two eigenvalues are treated as degenerate; defaults
         ``eps**0.6`` / ``eps**0.4``)
     method: str or callable or None
-        ``"exacteig"`` (default, dense), ``"davidson"`` (native HIP block Davidson), or a callable
+        ``"exacteig"`` (default, dense), ``"davidson"`` (native HIP block Davidson), ``"chebfsi"`` (Chebyshev-filtered
+        subspace iteration on the HIP kernels: a fixed block of ``neig + nguard`` vectors, for many pairs; ``M=None``; complex
+        blocks wider than 32 vectors solve their small eigenproblem with ``torch.linalg.eigh``), or a callable
         ``f(A, neig, mode, M, **fwd_options) -> (evals, evecs)``
     **fwd_options
         Method-specific options
@@ -111,7 +114,7 @@ def _custom_exacteig(A, neig, mode, M=None, **options):
     return exacteig(A, neig, mode, M)
 
 
-_SYMEIG_METHODS = {"davidson": davidson, "custom_exacteig": _custom_exacteig}
+_SYMEIG_METHODS = {"davidson": davidson, "chebfsi": chebfsi, "custom_exacteig": _custom_exacteig}
 
 
 class _SymeigFunction(torch.autograd.Function):
