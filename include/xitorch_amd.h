@@ -634,6 +634,54 @@ int xk_cheb_step_c64(const float* AY, long ldA, long sA, const float* Y, long ld
                      long ldP, long sP, float* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
                      void* stream);
 
+/* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (extension: svd method "gkl"; new symbols only, ABI stays 2) -
+ * xk_gkl_sweep: one Gram-Schmidt pass of one new vector per member against j <= xk_gkl_max_rows() rows of a basis
+ *   panel Q (Bt, cap, ldQ), rows are vectors (elements; complex elements for _c128 / _c64, interleaved storage):
+ *       dst[b,n] = s_b * ( w[b,n] - sum_{i<j} c[b,i] Q[b,i,n] ),  n < N,   s_b = scale ? scale[b] : 1
+ *   c[b,i] = coef[b * sC + i] (real) or coef[b * sC + 2i] + i coef[b * sC + 2i + 1] (complex), DOUBLES on the device;
+ *   coef NULL: no sum.  From the same read of Q it writes the partial sums over each chunk of xk_gkl_chunk_elems()
+ *   elements of conj(Q[b,i,:]) . dst[b,:] and of |dst[b,:]|^2 (of the values as stored) as doubles
+ *       part[(b * nval + r) * nchunk + chunk],  r < nval = j (complex: 2j; re, im interleaved) + 1 (sum of squares),
+ *   nchunk = ceil(N / chunk elements); part_len (doubles) must hold Bt * nval * nchunk.  The update is evaluated in
+ *   double and rounded once.  No atomics: a repeat call returns the same bits.  dst may BE w (same pointer and
+ *   stride) or lie apart from it; it must not touch rows [0, j) of Q (a slot of the panel that holds Q is fine: with
+ *   one batch stride for both, the footprints are compared member by member).  XK_ERR_ARG, nothing launched: Bt <= 0 or
+ *   > 65535, N <= 0, j < 0 or beyond the row cap, NULL w / dst / part (Q with j > 0), ldQ < N, a negative stride,
+ *   Bt > 1 with sD < N or sC below the coefficients of a member, overlapping ranges as above, a short part.
+ *   Bases 16 B aligned and pitch / strides multiples of the 16 B vector: 16 B non-temporal loads of the basis, all
+ *   issued before the first use; otherwise element by element.  Only dst[b, :N] is written.
+ * xk_gkl_finish: adds the partials of one sweep in a fixed order; coef[b * sC + r] = sum_r for r < nval - 1 (coef
+ *   may be NULL), nrm[b] = sqrt(sum of squares), rnrm[b] = its reciprocal, dst[b * sdst] = the norm (dst may be
+ *   NULL; the alpha / beta slot of the projected matrix), smax[b] = max(smax[b], norm) (may be NULL).  Breakdown —
+ *   norm <= u * smax[b] (the value before this call), or not finite —: norm and reciprocal are written as 0 and, when
+ *   brk is given and brk[b] < 0, brk[b] = code.
+ * xk_gkl_bsvd: SVD Bm[b] = P diag(sigma) Q^T of (Bt, n, n) row-major real matrices, n <= xk_gkl_bsvd_max(), by
+ *   one-sided Jacobi in double (never through Bm^T Bm).  sigma (Bt, n) descending (descending != 0) or ascending,
+ *   P, Q (Bt, n, n) row-major with the vectors as COLUMNS, orthonormal also where sigma is null, res[b,i] =
+ *   |beta[b] P[b, n-1, i]| (beta NULL: 0), status[4b..] = {number of i < k with res <= tol * max(sigma_max, smax[b]),
+ *   Jacobi sweeps, 1 if the sweep limit was hit, brk[b] (brk NULL: -1)}.  Bnext (may be NULL; not Bm; keep < n): the
+ *   projected matrix of the restarted basis, diag(sigma[:keep]) and column keep = beta * P[n-1, :keep]. */
+int xk_gkl_max_rows(void);
+int xk_gkl_bsvd_max(void);
+int xk_gkl_chunk_elems(int elem_bytes);
+int xk_gkl_sweep_f64(const double* Q, long ldQ, long sQ, const double* w, long sW, double* dst, long sD,
+                     const double* coef, long sC, const double* scale, double* part, long part_len, int Bt, int j,
+                     int N, void* stream);
+int xk_gkl_sweep_f32(const float* Q, long ldQ, long sQ, const float* w, long sW, float* dst, long sD,
+                     const double* coef, long sC, const double* scale, double* part, long part_len, int Bt, int j,
+                     int N, void* stream);
+int xk_gkl_sweep_c128(const double* Q, long ldQ, long sQ, const double* w, long sW, double* dst, long sD,
+                      const double* coef, long sC, const double* scale, double* part, long part_len, int Bt, int j,
+                      int N, void* stream);
+int xk_gkl_sweep_c64(const float* Q, long ldQ, long sQ, const float* w, long sW, float* dst, long sD,
+                     const double* coef, long sC, const double* scale, double* part, long part_len, int Bt, int j,
+                     int N, void* stream);
+int xk_gkl_finish(const double* part, int Bt, int nval, int nchunk, double* coef, long sC, double* nrm, double* rnrm,
+                  double* dst, long sdst, double* smax, double u, int* brk, int code, void* stream);
+int xk_gkl_bsvd(const double* Bm, const double* beta, const double* smax, const int* brk, int Bt, int n, int k,
+                int keep, int descending, double tol, double* sigma, double* P, double* Q, double* res, int* status,
+                double* Bnext, void* stream);
+
 /* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
  * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
  * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.

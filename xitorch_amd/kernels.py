@@ -1268,3 +1268,98 @@ def dense_wide(A, X, out=None):
                                                  Xrm.stride(1), Xrm.stride(0), ldy, sY, stream_ptr())
     check(rc, "xk_dense_wide")
     return out
+
+
+# --------------------------------------------------------------------------- Golub-Kahan-Lanczos kernels (xk_gkl.hip)
+GKL_MAX_ROWS = 64            # basis rows one xk_gkl_sweep reads (= the largest ncv)
+GKL_BSVD_MAX = 64            # order of the projected matrix xk_gkl_bsvd serves
+
+
+def gkl_chunks(N, dtype):
+    """number of chunks xk_gkl_sweep_* cuts a length-N vector of `dtype` into (one partial sum per chunk)"""
+    ce = fn("xk_gkl_chunk_elems")(torch.empty((), dtype=dtype).element_size())
+    return (N + ce - 1) // ce
+
+
+def gkl_nval(j, dtype):
+    """partial sums per member and chunk of a sweep over j rows: the j dots (complex: re, im) and the sum of squares"""
+    return (2 * j if dtype.is_complex else j) + 1
+
+
+def gkl_sweep(Q, j, w, dst, coef, scale, part, N, raw=False):
+    """dst[b,:N] = scale[b] * (w[b,:N] - sum_{i<j} coef[b,i] Q[b,i,:N]) and the partials of Q[b,:j]^H dst[b], |dst[b]|^2
+    (xk_gkl_sweep_*).  Q: (Bt, cap, ld) basis panel (rows are vectors; may be None when j == 0); w, dst: (Bt, L) views
+    with unit stride along the vector (dst may be w); coef: float64 rows of unit stride, (Bt, >= j) for real panels and
+    for complex panels the interleaved (re, im) pairs as (Bt, >= 2j) -- what gkl_finish writes and the driver passes --
+    or the same memory viewed (Bt, >= j, 2); None: no update; scale: (Bt,) float64 or None; part: 1-D float64 of at
+    least Bt * gkl_nval(j) * gkl_chunks(N)."""
+    require_device(w, "vector")
+    Bt = w.shape[0]
+    for t in (w, dst):
+        if t.dim() != 2 or t.shape[0] != Bt or t.dtype != w.dtype or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise _capi.NativeLibraryError("gkl_sweep: w and dst must be (Bt, L) of one dtype, unit stride along the vector")
+    if j > 0:
+        if Q.dim() != 3 or Q.dtype != w.dtype or Q.shape[0] != Bt or (Q.shape[2] > 1 and Q.stride(2) != 1):
+            raise _capi.NativeLibraryError("gkl_sweep: the basis must be a (Bt, cap, ld) panel of the vector's dtype")
+        if Q.shape[1] < j or Q.shape[2] < N:
+            raise _capi.NativeLibraryError("gkl_sweep: the basis panel has fewer than j rows or rows shorter than N")
+    if w.is_complex():
+        _require_resolved("gkl_sweep", Q, w, dst)
+    if (w.shape[1] < N or dst.shape[1] < N) and N > 0:
+        raise _capi.NativeLibraryError("gkl_sweep: a vector is shorter than N = %d" % N)
+    if coef is not None and (coef.dtype != torch.float64 or coef.shape[0] != Bt or coef.stride(-1) != 1 or
+                             (coef.dim() == 3 and coef.stride(1) != 2)):
+        raise _capi.NativeLibraryError("gkl_sweep: coef must be float64 (Bt, j) (complex: (Bt, 2j) or (Bt, j, 2)), contiguous rows")
+    if part.dtype != torch.float64 or not part.is_contiguous():
+        raise _capi.NativeLibraryError("gkl_sweep: part must be a contiguous float64 tensor")
+    one = Bt == 1
+    rc = fn("xk_gkl_sweep_" + suffix(w.dtype))(
+        ptr(Q if j > 0 else None), Q.stride(1) if j > 0 else 0, 0 if (one or j == 0) else Q.stride(0),
+        ptr(w), 0 if one else w.stride(0), ptr(dst), 0 if one else dst.stride(0),
+        ptr(coef), 0 if (coef is None or one) else coef.stride(0), ptr(scale), ptr(part), part.numel(),
+        Bt, int(j), int(N), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_gkl_sweep")
+    return dst
+
+
+def gkl_finish(part, Bt, nval, nchunk, coef, nrm, rnrm, dst=None, smax=None, u=0.0, brk=None, code=0, raw=False):
+    """fixed-order sums of a sweep's partials (xk_gkl_finish): coef[b, :nval-1] (may be None), nrm[b] = norm, rnrm[b] = 1 / norm,
+    dst[b] = norm for a (Bt,) float64 VIEW dst (e.g. Bm[:, j, j]; None: not stored), smax[b] = max(smax[b], norm);
+    breakdown (norm <= u * smax[b] or not finite): norm = 1 / norm = 0 and brk[b] = code where brk[b] < 0."""
+    require_device(part, "partials")
+    sdst = 0
+    if dst is not None:
+        if dst.dtype != torch.float64 or dst.dim() != 1 or dst.shape[0] != Bt:
+            raise _capi.NativeLibraryError("gkl_finish: dst must be a (Bt,) float64 view")
+        sdst = dst.stride(0) if Bt > 1 else 0
+    rc = fn("xk_gkl_finish")(ptr(part), Bt, int(nval), int(nchunk), ptr(coef),
+                             0 if (coef is None or Bt == 1) else coef.stride(0), ptr(nrm), ptr(rnrm), ptr(dst), sdst,
+                             ptr(smax),
+                             float(u), ptr(brk), int(code), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_gkl_finish")
+
+
+def gkl_bsvd(Bm, beta=None, smax=None, brk=None, k=0, keep=0, descending=True, tol=0.0, Bnext=None, out=None,
+             raw=False):
+    """SVD of the (Bt, n, n) float64 projected matrices by one-sided Jacobi in LDS (xk_gkl_bsvd), n <= 64.  Returns
+    (sigma (Bt, n) in the asked order, P, Q (Bt, n, n) vectors as columns, res (Bt, n) = |beta P[n-1, :]|,
+    status (Bt, 4) int32 = converged among the first k / sweeps / sweep-limit flag / breakdown code).  Bnext: receives
+    the projected matrix of the restarted basis (keep < n).  out: a tuple of the five outputs to reuse."""
+    require_device(Bm, "projected matrix")
+    if Bm.dtype != torch.float64 or Bm.dim() != 3 or Bm.shape[1] != Bm.shape[2] or not Bm.is_contiguous():
+        raise _capi.NativeLibraryError("gkl_bsvd: Bm must be a contiguous (Bt, n, n) float64 tensor")
+    Bt, n = Bm.shape[0], Bm.shape[1]
+    if out is None:
+        mk = lambda *s: torch.empty(s, dtype=torch.float64, device=Bm.device)
+        out = (mk(Bt, n), mk(Bt, n, n), mk(Bt, n, n), mk(Bt, n), torch.zeros((Bt, 4), dtype=torch.int32, device=Bm.device))
+    sigma, P, Q, res, status = out
+    rc = fn("xk_gkl_bsvd")(ptr(Bm), ptr(beta), ptr(smax), ptr(brk), Bt, n, int(k), int(keep), 1 if descending else 0,
+                           float(tol), ptr(sigma), ptr(P), ptr(Q), ptr(res), ptr(status), ptr(Bnext), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_gkl_bsvd")
+    return out

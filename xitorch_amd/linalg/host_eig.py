@@ -15,9 +15,9 @@ from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
 from xitorch_amd.dist import allreduce_max_
 
-__all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard"]
+__all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard", "gkl", "gkl_default_ncv"]
 
-calls = {"davidson": 0, "chebfsi": 0}
+calls = {"davidson": 0, "chebfsi": 0, "gkl": 0}
 
 
 def _H(x):
@@ -323,3 +323,214 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     if mode != "lowest":
         evals, evecs = evals.flip(-1), evecs.flip(-1)
     return evals, evecs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Golub-Kahan-Lanczos bidiagonalisation with thick restart (extension; Baglama & Reichel, SIAM J. Sci. Comput. 27 (2005)
+# 19; full reorthogonalisation as in Larsen's PROPACK): svd(method="gkl")
+# ---------------------------------------------------------------------------------------------------------------------
+GKL_MAX_NCV = 64             # order of the projected matrix the native small SVD serves (xk_gkl_bsvd)
+
+
+def gkl_default_ncv(k, short):
+    """basis size: min(max(2k + 8, 20), short side)"""
+    return min(max(2 * k + 8, 20), short)
+
+
+def _gkl_setup(A, k, mode, ncv, process_group):
+    """argument checks and sizes shared by the host twin and the device driver: (m, n, tall, mm, nn, k, ncv, keep,
+    dense) with mm >= nn the sides of the operator the iteration runs on (A, or A^H when m < n) and dense = the
+    problem is handed to the dense SVD (short side <= max(2k, 16))."""
+    if process_group is not None:
+        raise NotImplementedError("gkl: batch sharding over a process group is not supported by the Golub-Kahan-"
+                                  "Lanczos iteration; use method='davidson'")
+    if mode not in ("lowest", "uppest"):
+        raise ValueError("gkl: mode must be 'lowest' or 'uppest'/'uppermost', got %r" % (mode,))
+    m, n = A.shape[-2], A.shape[-1]
+    tall = m >= n
+    mm, nn = (m, n) if tall else (n, m)
+    if k is None:
+        k = nn
+    if k < 1 or k > nn:
+        raise ValueError("gkl: k = %d singular triplets asked of an operator whose short side is %d" % (k, nn))
+    dense = nn <= max(2 * k, 16)
+    if ncv is None:
+        ncv = gkl_default_ncv(k, nn)
+        if not dense and ncv > GKL_MAX_NCV:
+            raise ValueError("gkl: k = %d needs a basis of %d > %d vectors, beyond the native small SVD; pass a "
+                             "smaller ncv (> k) or use method='davidson'" % (k, ncv, GKL_MAX_NCV))
+    ncv = int(ncv)
+    if ncv > GKL_MAX_NCV:
+        raise ValueError("gkl: ncv = %d is beyond the native small SVD (ncv <= %d)" % (ncv, GKL_MAX_NCV))
+    if not dense and k > ncv - 1:
+        raise ValueError("gkl: k = %d needs ncv >= k + 1 (got ncv = %d)" % (k, ncv))
+    if not dense and ncv > nn:
+        raise ValueError("gkl: ncv = %d exceeds the short side %d of the operator" % (ncv, nn))
+    keep = k + (ncv - k) // 2
+    return m, n, tall, mm, nn, k, ncv, keep, dense
+
+
+def _gkl_dense(A, k, mode):
+    """the hand-off of small problems: the library SVD of the full matrix, k triplets, sigma ascending"""
+    Uf, S, Vh = torch.linalg.svd(A.fullmatrix(), full_matrices=False)               # sigma descending
+    if mode == "lowest":
+        idx = torch.arange(S.shape[-1] - 1, S.shape[-1] - 1 - k, -1, device=S.device)      # smallest first
+    else:
+        idx = torch.arange(k - 1, -1, -1, device=S.device)                           # the k largest, ascending
+    return Uf.index_select(-1, idx), S.index_select(-1, idx), _H(Vh).index_select(-1, idx)
+
+
+def _gkl_start_vector(A, V0, v_init, bdims, B, nn, tall, dtype, dev, rng_device):
+    """(B, nn) start vector on the SHORT side.  V0 (*batch, n, k0) holds guesses of right singular vectors of A: their
+    sum starts the iteration (through A when the short side is the left one)."""
+    from xitorch_amd.linalg.native_eig import _initial_block
+    if V0 is not None:
+        if V0.shape[-2] != A.shape[-1]:
+            raise RuntimeError("V0 must have shape (*batch, %d, k0), got %s" % (A.shape[-1], tuple(V0.shape)))
+        v = V0.to(device=dev, dtype=dtype).sum(dim=-1, keepdim=True)
+        if not tall:
+            v = A.mm(v)
+        return v.expand(*bdims, nn, 1).reshape(B, nn)
+    return _initial_block(v_init, None, bdims, B, nn, 1, dtype, dev, rng_device).reshape(B, nn)
+
+
+def _gkl_random(gen, B, N, dtype):
+    """(B, N) replacement vectors after a breakdown: drawn on the host from the run's own generator"""
+    rd = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    return torch.randn((B, N), dtype=rd, generator=gen).to(dtype)
+
+
+def gkl(A, k, mode, max_niter=100, min_eps=1e-6, ncv=None, V0=None, v_init="randn", rng_device="cpu", verbose=False,
+        trace=None, process_group=None, **unused):
+    """Golub-Kahan-Lanczos bidiagonalisation with thick restart in torch ops for an operator in HOST memory: the
+    statement of `native_gkl.gkl` (same options, same refusals, same decisions).  Works on A itself — never on A^H A —
+    always in the tall orientation (A^H when m < n).  Per Lanczos step one apply of A and one of A^H, each new vector
+    orthogonalised against its whole basis by two classical Gram-Schmidt passes; alpha and beta are the norms.  A cycle
+    fills the basis to ncv vectors, takes the SVD of the projected matrix (upper bidiagonal plus the restart arrow),
+    and keeps k + (ncv - k) // 2 plain Ritz triplets.  Returns (u (*B, m, k), s (*B, k) ASCENDING like svd's other
+    route, v (*B, n, k))."""
+    import warnings
+    from xitorch_amd._util import ConvergenceWarning
+    calls["gkl"] += 1
+    dev = torch.device(A.device)
+    if dev.type != "cpu":
+        raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "
+                                 "run on the HIP kernels" % dev)
+    m, n, tall, mm, nn, k, ncv, keep, dense = _gkl_setup(A, k, mode, ncv, process_group)
+    if dense:
+        if trace is not None:
+            trace.update(niter=0, napply=0, ncv=ncv, handed_to="dense_svd")
+        return _gkl_dense(A, k, mode)
+    dtype = A.dtype
+    bdims = list(A.shape[:-2])
+    B = 1
+    for d in bdims:
+        B *= d
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    u_round = torch.finfo(rdt).eps
+    napply = 0
+
+    def apply(x, adjoint):
+        # x (B, len) -> (B, len'); the iteration's operator is A (tall) or A^H
+        nonlocal napply
+        napply += 1
+        X = x.reshape(*bdims, x.shape[-1], 1)
+        Y = A.rmm(X) if (adjoint == tall) else A.mm(X)
+        return Y.expand(*bdims, Y.shape[-2], 1).reshape(B, Y.shape[-2])
+
+    U = torch.zeros((B, mm, ncv), dtype=dtype)
+    V = torch.zeros((B, nn, ncv + 1), dtype=dtype)
+    Bm = torch.zeros((B, ncv, ncv), dtype=torch.float64)
+    beta = torch.zeros((B,), dtype=torch.float64)
+    smax = torch.zeros((B,), dtype=torch.float64)
+    gen = torch.Generator().manual_seed(12421 + 7)
+    breakdowns = []
+
+    def orth(w, Q, code):
+        """two classical Gram-Schmidt passes of w (B, len) against Q (B, len, j); (unit vector, norm (B,) float64);
+        a member whose norm is <= u * (largest norm so far) breaks down: norm 0, a fresh random unit vector orthogonal
+        to Q takes its place"""
+        nonlocal smax
+        for _ in range(2):
+            if Q.shape[-1]:
+                w = w - torch.matmul(Q, torch.matmul(_H(Q), w.unsqueeze(-1))).squeeze(-1)
+        nrm = torch.linalg.vector_norm(w, dim=-1).to(torch.float64)
+        bad = ~(nrm > u_round * smax) | ~torch.isfinite(nrm)
+        if bool(bad.any()):
+            breakdowns.append((code, bad.nonzero().flatten().tolist()))
+            r = _gkl_random(gen, B, w.shape[-1], dtype)
+            for _ in range(2):
+                if Q.shape[-1]:
+                    r = r - torch.matmul(Q, torch.matmul(_H(Q), r.unsqueeze(-1))).squeeze(-1)
+            r = r / torch.linalg.vector_norm(r, dim=-1, keepdim=True)
+            w = torch.where(bad.unsqueeze(-1), r, w / torch.where(bad, torch.ones_like(nrm), nrm).to(rdt).unsqueeze(-1))
+            nrm = torch.where(bad, torch.zeros_like(nrm), nrm)
+        else:
+            w = w / nrm.to(rdt).unsqueeze(-1)
+        smax = torch.maximum(smax, nrm)
+        return w, nrm
+
+    v0 = _gkl_start_vector(A, V0, v_init, bdims, B, nn, tall, dtype, dev, rng_device)
+    nv0 = torch.linalg.vector_norm(v0, dim=-1, keepdim=True)
+    if bool((nv0 == 0).any()):
+        raise RuntimeError("gkl: the start vector is zero")
+    V[:, :, 0] = v0 / nv0
+    start, niter, history, conv_history, done = 0, 0, [], [], False
+    descending = mode != "lowest"
+    for cycle in range(max_niter):
+        niter = cycle + 1
+        for j in range(start, ncv):
+            w, al = orth(apply(V[:, :, j], False), U[:, :, :j], 2 * j)
+            U[:, :, j] = w
+            Bm[:, j, j] = al
+            w, be = orth(apply(U[:, :, j], True), V[:, :, :j + 1], 2 * j + 1)
+            V[:, :, j + 1] = w
+            if j + 1 < ncv:
+                Bm[:, j, j + 1] = be
+            else:
+                beta = be
+        P, S, Qh = torch.linalg.svd(Bm)
+        Q = Qh.transpose(-2, -1)
+        if not descending:
+            P, S, Q = P.flip(-1), S.flip(-1), Q.flip(-1)
+        rho = beta.unsqueeze(-1) * P[:, -1, :]
+        res = rho.abs()
+        scale = torch.maximum(S.max(dim=-1)[0], smax)
+        nconv = (res[:, :k] <= min_eps * scale.unsqueeze(-1)).sum(dim=-1)
+        history.append(float((res[:, :k] / scale.unsqueeze(-1)).max()))
+        conv_history.append(nconv.tolist())
+        if verbose:
+            print("Cycle %3d (basis of %d): max |beta P[last, i]| / sigma_max = %.3e, converged %s"
+                  % (niter, ncv, history[-1], nconv.tolist()))
+        if bool((nconv >= k).all()):
+            done = True
+            break
+        if cycle + 1 == max_niter:
+            break
+        Pc, Qc = P[:, :, :keep].to(dtype), Q[:, :, :keep].to(dtype)
+        Vn = torch.zeros_like(V)
+        Vn[:, :, :keep] = torch.matmul(V[:, :, :ncv], Qc)
+        Vn[:, :, keep] = V[:, :, ncv]
+        Un = torch.zeros_like(U)
+        Un[:, :, :keep] = torch.matmul(U, Pc)
+        U, V = Un, Vn
+        Bm = torch.zeros_like(Bm)
+        idx = torch.arange(keep)
+        Bm[:, idx, idx] = S[:, :keep]
+        Bm[:, idx, keep] = rho[:, :keep]
+        start = keep
+    if not done:
+        warnings.warn(ConvergenceWarning("gkl: convergence is not achieved after %d restart cycles (max |beta P[last, i]| "
+                                         "/ sigma_max = %.3e > min_eps = %.3e); the last Ritz block is returned"
+                                         % (niter, history[-1], min_eps)))
+    uu = torch.matmul(U, P[:, :, :k].to(dtype))
+    vv = torch.matmul(V[:, :, :ncv], Q[:, :, :k].to(dtype))
+    ss = S[:, :k].to(rdt)
+    if descending:
+        uu, vv, ss = uu.flip(-1), vv.flip(-1), ss.flip(-1)
+    if not tall:
+        uu, vv = vv, uu
+    if trace is not None:
+        trace.update(niter=niter, restarts=niter - 1, napply=napply, ncv=ncv, keep=keep, resid_history=history,
+                     converged_history=conv_history, breakdowns=breakdowns, host_reads=None, panel_kernel="host", tall=tall, converged=done)
+    return uu.reshape(*bdims, m, k), ss.reshape(*bdims, k), vv.reshape(*bdims, n, k)

@@ -90,9 +90,35 @@ def svd(A, k=None, mode="uppest", bck_options={}, method=None, **fwd_options):
     Singular value decomposition :math:`\mathbf{A} = \mathbf{U\Sigma V}^H` of an operator
     ``(*BA, m, n)`` through ``symeig`` of ``A^H A`` or ``A A^H`` (whichever is smaller).
     Returns ``(u (*BA,m,k), s (*BA,k), vh (*BA,k,n))``.  (reference: symeig.py:146-250)
+
+    ``method="gkl"`` (extension; every other value keeps the route above) works on ``A`` itself: Golub-Kahan-Lanczos
+    bidiagonalisation with thick restart on the HIP kernels (``native_gkl.gkl``; an operator in host memory is served
+    by ``host_eig.gkl``).  The route above squares the condition number, so a singular value below
+    ``sqrt(eps) * sigma_max`` comes back as noise; ``gkl`` returns every wanted triplet to about
+    ``min_eps * sigma_max``, ``mode="lowest"`` included.  Forward options: ``ncv`` (basis size, ``k < ncv <= 64``,
+    default ``min(max(2k + 8, 20), min(m, n))``), ``max_niter`` (restart cycles), ``min_eps`` (a triplet is converged
+    when ``|beta P[last, i]| <= min_eps * sigma_max``), ``V0`` (``(*BA, n, k0)`` guesses of right singular vectors),
+    ``v_init``, ``verbose``, ``trace``.  ``process_group`` raises ``NotImplementedError``; ``k > ncv - 1`` or
+    ``ncv > 64`` raise ``ValueError``; a problem whose short side is ``<= max(2k, 16)`` goes to ``torch.linalg.svd``.
+    When ``max_niter`` ends first the last Ritz block is returned with a ``ConvergenceWarning`` (thick restart keeps
+    the wanted triplets, so no separate best block is tracked).  A breakdown (``alpha`` or ``beta`` below
+    ``u * sigma_max``) never raises: the member continues from a random vector; on the device each recovery costs one
+    more read of the status words and a rerun of the rest of the cycle, so keep ``ncv`` below the numerical rank.
+    ``RuntimeError`` is raised only for a zero start vector or a projected SVD that hits its sweep limit.
+    ``s`` is ascending, as on the other route; ``u`` carries the iteration's own orthonormality (it is not
+    ``A v / clamp(s)``).
+
+    Gradient of ``method="gkl"``: the triplets are eigenpairs ``(s, [u; v] / sqrt(2))`` of the Hermitian augmented
+    operator ``[[0, A], [A^H, 0]]``, and ``symeig``'s implicit backward is applied to that operator unchanged: one
+    shifted solve per backward pass.  That system is indefinite, so the backward solver defaults to
+    ``bck_options={"method": "minres"}`` (any ``method`` given in ``bck_options`` is respected).  For ``m != n`` the
+    augmented operator has ``|m - n|`` zero eigenvalues: the backward of a triplet with ``s`` close to 0 is
+    ill-conditioned.  The loss must not depend on the phase of a pair ``(u_i, v_i)``.
     """
     if is_debug_enabled():
         A.check()
+    if method == "gkl":
+        return _svd_gkl(A, k, mode, bck_options, fwd_options)
     m, n = A.shape[-2], A.shape[-1]
     if m < n:
         AA = A.matmul(A.H, is_hermitian=True)
@@ -108,6 +134,56 @@ def svd(A, k=None, mode="uppest", bck_options={}, method=None, **fwd_options):
         v = evecs
         u = A.mm(v) / sdiv
     return u, s, v.transpose(-2, -1).conj()
+
+
+class _AugmentedOperator(LinearOperator):
+    """The Hermitian operator ``[[0, A], [A^H, 0]]`` of order m + n whose eigenpairs with positive eigenvalue are
+    ``(sigma, [u; v] / sqrt(2))``: what the implicit backward of ``svd(method="gkl")`` differentiates.  Its parameters
+    are A's."""
+
+    def __init__(self, A):
+        m, n = A.shape[-2], A.shape[-1]
+        super().__init__(shape=(*A.shape[:-2], m + n, m + n), is_hermitian=True, dtype=A.dtype, device=A.device,
+                         _suppress_hermit_warning=True)
+        self.A = A
+        self._m = m
+
+    def _mv(self, x):
+        return self._mm(x.unsqueeze(-1)).squeeze(-1)
+
+    def _mm(self, x):
+        m = self._m
+        return torch.cat((self.A.mm(x[..., m:, :]), self.A.rmm(x[..., :m, :])), dim=-2)
+
+    def _getparamnames(self, prefix=""):
+        return self.A._getparamnames(prefix=prefix + "A.")
+
+
+def _svd_gkl(A, k, mode, bck_options, fwd_options):
+    from xitorch_amd.linalg.native_gkl import gkl
+    mode = mode.lower()
+    if mode == "uppermost":
+        mode = "uppest"
+    m, n = A.shape[-2], A.shape[-1]
+    if k is None:
+        k = min(m, n)
+    wants_grad = torch.is_grad_enabled() and A.is_getparamnames_implemented and \
+        any(p.requires_grad for p in A.getlinopparams())
+    if not wants_grad:
+        with torch.no_grad():
+            u, s, v = gkl(A, k, mode, **fwd_options)
+        return u, s, v.transpose(-2, -1).conj()
+    rt2 = 2.0 ** 0.5
+
+    def method(aug, neig, mode_, M, **opts):
+        u, s, v = gkl(aug.A, neig, mode, **opts)
+        return s, torch.cat((u, v), dim=-2) / rt2
+
+    bck = dict(bck_options)
+    bck.setdefault("method", "minres")
+    evals, evecs = symeig(_AugmentedOperator(A), k, mode, bck_options=bck, method=method, **fwd_options)
+    u, v = evecs[..., :m, :] * rt2, evecs[..., m:, :] * rt2
+    return u, evals, v.transpose(-2, -1).conj()
 
 
 def _custom_exacteig(A, neig, mode, M=None, **options):
