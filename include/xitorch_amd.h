@@ -682,6 +682,33 @@ int xk_gkl_bsvd(const double* Bm, const double* beta, const double* smax, const 
                 int keep, int descending, double tol, double* sigma, double* P, double* Q, double* res, int* status,
                 double* Bnext, void* stream);
 
+/* ---- factorised sparse approximate inverse of a Hermitian CSR operator (extension: linalg.fsai; new symbols only, ABI
+ * stays 2) -----------------------------------------------------------------------------------------------------------
+ * xk_fsai_build: the values of the lower-triangular G with G A G^H ~ I on a given pattern.  Row i of G has the columns
+ *   S_i = g_idx[g_ptr[i] .. g_ptr[i+1]): ascending, unique, all <= i, i itself LAST, 1 <= |S_i| <= xk_fsai_max_row().
+ *   With A_JJ = A[S_i, S_i] = L L^H and L^H z = e_m the row is conj(z): diag(G A G^H) = 1, (G A)[i, j] = 0 for j in
+ *   S_i other than i, G[i,i] real positive.  Of A (CSR a_ptr (N+1), a_idx, values a_val[b * sV + k], sV = 0 broadcasts
+ *   one set over the batch) only the entries with column <= row are read and A is taken as Hermitian; duplicates add
+ *   up in storage order, columns need not be sorted, the imaginary part of a diagonal entry is ignored.  a_nnz / g_nnz:
+ *   the stored entries per member of A / of G (the kernel reads and writes no index beyond them).
+ *   G values g_val[b * sG + k].  One wavefront per (row, member), no floating-point atomics: bit-reproducible.
+ *   A row whose A_JJ is not numerically positive definite (a pivot <= 0 or not finite, or a solution that is not
+ *   finite) becomes the Jacobi row, G[i,i] = 1 / sqrt(|a_ii|) (1 when a_ii is 0 or not finite), zeros elsewhere, and is
+ *   counted in nfail[b] (B ints, zeroed by the call).  A row of the pattern outside the limits above is left
+ *   unwritten and counted as well: the caller checks the pattern.
+ *   XK_ERR_ARG (decided on the host, before any launch): a null pointer, N <= 0, B <= 0, a negative stride or count,
+ *   g_nnz < N, members of G (or of A with sV != 0) that overlap, g_val overlapping a_val.
+ *   Complex (_c128 / _c64): interleaved (re, im); strides and counts in whole complex elements. */
+int xk_fsai_max_row(void);
+int xk_fsai_build_f64(const int* a_ptr, const int* a_idx, const double* a_val, long sV, int a_nnz, const int* g_ptr,
+                      const int* g_idx, double* g_val, long sG, int g_nnz, int* nfail, int N, int B, void* stream);
+int xk_fsai_build_f32(const int* a_ptr, const int* a_idx, const float* a_val, long sV, int a_nnz, const int* g_ptr,
+                      const int* g_idx, float* g_val, long sG, int g_nnz, int* nfail, int N, int B, void* stream);
+int xk_fsai_build_c128(const int* a_ptr, const int* a_idx, const double* a_val, long sV, int a_nnz, const int* g_ptr,
+                       const int* g_idx, double* g_val, long sG, int g_nnz, int* nfail, int N, int B, void* stream);
+int xk_fsai_build_c64(const int* a_ptr, const int* a_idx, const float* a_val, long sV, int a_nnz, const int* g_ptr,
+                      const int* g_idx, float* g_val, long sG, int g_nnz, int* nfail, int N, int B, void* stream);
+
 /* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
  * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
  * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.

@@ -161,6 +161,9 @@ def _declare(L):
         sigs["xk_gkl_sweep_" + sfx] = (I, [P, Lg, Lg, P, Lg, P, Lg, P, Lg, P, P, Lg, I, I, I, P])
     sigs["xk_gkl_finish"] = (I, [P, I, I, I, P, Lg, P, P, P, Lg, P, D, P, I, P])
     sigs["xk_gkl_bsvd"] = (I, [P, P, P, P, I, I, I, I, I, D, P, P, P, P, P, P, P])
+    sigs["xk_fsai_max_row"] = (I, [])
+    for sfx in ("f64", "f32", "c128", "c64"):
+        sigs["xk_fsai_build_" + sfx] = (I, [P, P, P, Lg, I, P, P, P, Lg, I, P, I, I, P])
     sigs["xk_herm_eigh_lds_bytes"] = (Lg, [I, I, I])
     sigs["xk_herm_eigh_workspace_elems"] = (Lg, [I, I, I])
     for sfx in ("c128", "c64"):

@@ -1363,3 +1363,66 @@ def gkl_bsvd(Bm, beta=None, smax=None, brk=None, k=0, keep=0, descending=True, t
         return rc
     check(rc, "xk_gkl_bsvd")
     return out
+
+
+# --------------------------------------------------------------------------- FSAI preconditioner build
+def fsai_max_row():
+    return int(fn("xk_fsai_max_row")())
+
+
+def fsai_check_pattern(g_ptr, g_idx, N):
+    """The contract of xk_fsai_build on the pattern of G, checked once in torch ops: every row has between 1 and
+    xk_fsai_max_row() columns, ascending and unique, none beyond the row index, the row index itself last."""
+    if g_ptr.dtype != torch.int32 or g_idx.dtype != torch.int32 or g_ptr.dim() != 1 or g_idx.dim() != 1 or \
+            g_ptr.numel() != N + 1 or not g_ptr.is_contiguous() or not g_idx.is_contiguous():
+        raise _capi.NativeLibraryError("fsai: the pattern of G must be contiguous int32 arrays, g_ptr of N + 1 entries")
+    p = g_ptr.to(torch.int64)
+    lens = p[1:] - p[:-1]
+    if int(p[0]) != 0 or int(p[-1]) != g_idx.numel() or int(lens.min()) < 1:
+        raise _capi.NativeLibraryError("fsai: g_ptr must run from 0 to the entry count and leave no row empty")
+    if int(lens.max()) > fsai_max_row():
+        raise _capi.NativeLibraryError("fsai: a row of G has %d columns, the kernel's cap is %d"
+                                       % (int(lens.max()), fsai_max_row()))
+    rows = torch.arange(N, dtype=torch.int64, device=g_ptr.device)
+    idx = g_idx.to(torch.int64)
+    if not bool((idx[p[1:] - 1] == rows).all()):
+        raise _capi.NativeLibraryError("fsai: the last column of every row of G must be the row index")
+    row_of = torch.repeat_interleave(rows, lens, output_size=idx.numel())
+    if int(idx.min()) < 0 or not bool((idx <= row_of).all()):
+        raise _capi.NativeLibraryError("fsai: G is lower triangular, a column index lies outside [0, row]")
+    if idx.numel() > 1 and not bool(((idx[1:] > idx[:-1]) | (row_of[1:] != row_of[:-1])).all()):
+        raise _capi.NativeLibraryError("fsai: the columns of a row of G must be ascending and unique")
+
+
+def fsai_build(a_ptr, a_idx, a_val, g_ptr, g_idx, N, out=None, nfail=None, check_pattern=True, raw=False):
+    """The FSAI values on the pattern (g_ptr, g_idx) of the Hermitian CSR operator (a_ptr, a_idx, a_val) (xk_fsai_build_*):
+    a_val (B, nnz) rows of unit stride (B = 1 for values shared by a batch: G is shared then as well); returns
+    (g_val (B, g_nnz), nfail (B,) int32 = rows that fell back to the Jacobi row).  fp64 / fp32 / complex128 /
+    complex64; complex values must be resolved."""
+    require_device(a_val, "values")
+    if a_val.is_complex():
+        _require_resolved("fsai_build", a_val, out)
+    for t in (a_ptr, a_idx, g_ptr, g_idx):
+        if t.dtype != torch.int32 or t.device != a_val.device or not t.is_contiguous():
+            raise _capi.NativeLibraryError("fsai_build: index arrays must be contiguous int32 on the values' device")
+    a_nnz, g_nnz = a_idx.numel(), g_idx.numel()
+    if a_ptr.numel() != N + 1 or a_val.dim() != 2 or a_val.shape[1] != a_nnz or (a_nnz > 1 and a_val.stride(1) != 1):
+        raise _capi.NativeLibraryError("fsai_build: a_ptr must have N + 1 entries and the values be (B, %d) rows of "
+                                       "unit stride, got %s" % (a_nnz, tuple(a_val.shape)))
+    if check_pattern:
+        fsai_check_pattern(g_ptr, g_idx, N)
+    B = a_val.shape[0]
+    if out is None:
+        out = torch.zeros((B, g_nnz), dtype=a_val.dtype, device=a_val.device)
+    if out.shape != (B, g_nnz) or out.dtype != a_val.dtype or not out.is_contiguous():
+        raise _capi.NativeLibraryError("fsai_build: the output must be a contiguous (%d, %d) tensor" % (B, g_nnz))
+    if nfail is None:
+        nfail = torch.zeros((B,), dtype=torch.int32, device=a_val.device)
+    rc = fn("xk_fsai_build_" + suffix(a_val.dtype))(ptr(a_ptr), ptr(a_idx), ptr(a_val),
+                                                    a_val.stride(0) if B > 1 else 0, a_nnz, ptr(g_ptr), ptr(g_idx),
+                                                    ptr(out), out.stride(0) if B > 1 else 0, g_nnz, ptr(nfail), int(N),
+                                                    B, stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_fsai_build")
+    return out, nfail

@@ -1,4 +1,5 @@
 from xitorch_amd.linalg.solve import solve
 from xitorch_amd.linalg.symeig import symeig, lsymeig, usymeig, svd
+from xitorch_amd.linalg.precond import fsai, FSAIOperator
 
-__all__ = ["solve", "symeig", "lsymeig", "usymeig", "svd"]
+__all__ = ["solve", "symeig", "lsymeig", "usymeig", "svd", "fsai", "FSAIOperator"]

@@ -9,6 +9,7 @@ out[b, c, :N] = A_b x[b, c, :N] (or A_b^H) without any layout copies for the nat
   BandedLinearOperator  -> xk_banded_mm
   SparseLinearOperator  -> xk_csr_mm     (fp32 / fp64 / complex64 / complex128 values; the adjoint on the pattern's
                                           CSC view, complex values conjugated by the kernel)
+  FSAIOperator          -> xk_csr_mm twice (G, then G^H on G's CSC view) through a cached scratch panel
   anything else         -> the operator's own .mm/.rmm on the (.., N, p) strided view
 """
 import torch
@@ -39,12 +40,13 @@ def from_panel(P, bdims, N):
 class PanelOperator:
     def __init__(self, A, bdims, Bt, N):
         from xitorch_amd.linop import MatrixLinearOperator, BandedLinearOperator, SparseLinearOperator
+        from xitorch_amd.linalg.precond import FSAIOperator
         self.A, self.bdims, self.Bt, self.N = A, list(bdims), Bt, N
         self.kind = "generic"
         self.symm = False
         self.symm_narrow = False
         self.napply = 0
-        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded / csr)
+        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded / csr / fsai)
         self.events = None          # when a list: (start, end, p) HIP events around every native launch
         self.hermitian = bool(getattr(A, "is_hermitian", False))
         nA = 1
@@ -90,6 +92,18 @@ class PanelOperator:
             self.vals = A.values.resolve_conj().reshape(-1, A.nnz)     # (a lazily conjugated view: its numbers)
             if A.nnz > 1 and self.vals.stride(-1) != 1:
                 self.vals = self.vals.contiguous()
+        elif isinstance(A, FSAIOperator) and (native_t(A.G.values) or native_c(A.G.values)) and \
+                (nA == Bt or nA == 1):
+            # P = G^H G: two CSR products on the padded panels
+            G = A.G
+            self.kind = "fsai"
+            self.cplx = native_c(G.values)
+            self.pat = G._pattern
+            self.pat.csc()                    # the view of G^H, built here rather than in the first iteration
+            self.vals = G.values.resolve_conj().reshape(-1, G.nnz)
+            if G.nnz > 1 and self.vals.stride(-1) != 1:
+                self.vals = self.vals.contiguous()
+            self._scratch = None              # G x; reallocated only when the column count grows
 
     def diagonal(self):
         """diag(A) as a contiguous (nA, N) array (native operators only)."""
@@ -195,6 +209,15 @@ class PanelOperator:
         elif self.kind == "csr":
             self.last_kernel = "csr"
             K.csr_mm(self.pat, self.vals, X[:, :, :N], out=out[:, :, :N], trans=trans)
+        elif self.kind == "fsai":
+            self.last_kernel = "fsai"
+            p = X.shape[1]
+            if self._scratch is None or self._scratch.shape[0] != X.shape[0] or self._scratch.shape[1] < p or \
+                    self._scratch.dtype != X.dtype:
+                self._scratch = torch.empty((X.shape[0], p, N), dtype=X.dtype, device=X.device)
+            scr = self._scratch[:, :p]
+            K.csr_mm(self.pat, self.vals, X[:, :, :N], out=scr, trans=False)
+            K.csr_mm(self.pat, self.vals, scr, out=out[:, :, :N], trans=True)
         else:
             self.last_kernel = "banded"
             K.banded_mm(self.band, X[:, :, :N], out=out[:, :, :N], trans=trans)

@@ -34,7 +34,8 @@ def solve(A, B, E=None, M=None, bck_options={}, method=None, **fwd_options):
         made for Hermitian indefinite or consistent singular operators.  A callable ``f(A, B, E, M, **fwd_options) -> X``
         plugs in a user method.
     **fwd_options
-        Method-specific options
+        Method-specific options.  For ``"cg"`` and ``"minres"`` the option ``precond`` (here or in ``bck_options``)
+        also takes the string ``"fsai"``: ``linalg.fsai(A)`` with its defaults, for a ``SparseLinearOperator`` ``A``
     """
     assert_runtime(A.shape[-1] == A.shape[-2], "The linear operator A must have a square shape")
     assert_runtime(A.shape[-1] == B.shape[-2], "Mismatch shape of A & B (A: %s, B: %s)" % (A.shape, B.shape))
@@ -100,6 +101,11 @@ class _SolveFunction(torch.autograd.Function):
                     "minres": nk.minres,
                     "scipy_gmres": nk.scipy_gmres,
                 }
+                if isinstance(config.get("precond"), str) and method in ("cg", "minres"):
+                    # a named preconditioner, built once per call from the operator as it is now (the backward solve
+                    # comes through here again with bck_options)
+                    from xitorch_amd.linalg.precond import named_preconditioner
+                    config["precond"] = named_preconditioner(config["precond"], A, method)
                 x = get_method("solve", methods, method)(A, B, E, M, **config)
         ctx.e_is_none = E is None
         ctx.A, ctx.M, ctx.na = A, M, na
