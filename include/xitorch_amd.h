@@ -772,6 +772,58 @@ int xk_broyden_axpy_f64(double* out, const double* u0, double g0, const double* 
 int xk_broyden_axpy_f32(float* out, const float* u0, double g0, const float* u1, double g1, const float* V, long ldv,
                         const float* coef, const float* scale, int k, double gamma, long L, void* stream);
 
+/* ---- LSMR step kernels (xk_lsmr.hip; extension, no reference counterpart): least squares min |A x - b|^2 + damp^2 |x|^2
+ * with a rectangular operator (Fong & Saunders 2011).  Vectors are (S, ld) arrays as above (u side: length m, v side:
+ * length n; _c128 / _c64: interleaved complex, N and ld in complex elements); partial buffers are
+ * (S, xk_kry_max_partials()) REAL elements of the vector's precision.  The per-system scalars are DOUBLES whatever the
+ * vector type: state is (2, S, xk_lsmr_state_len()) doubles, step k reads slot k & 1 and xk_lsmr_update writes slot
+ * (k + 1) & 1.  Entry i of a slot: 0 alpha (0: start), 1 beta, 2 alphabar, 3 zetabar, 4 rho, 5 rhobar, 6 cbar, 7 sbar,
+ * 8 zeta, 9 betadd, 10 betad, 11 rhodold, 12 tautildeold, 13 thetatilde, 14 d, 15 normA^2, 16 maxrbar, 17 minrbar,
+ * 18 steps taken, 19 stop code (0 running, 1 S1, 2 S2, 3 S3 = conlim, 4 alpha = 0, 5 beta = 0), 20 |b|, 21 |rbar|,
+ * 22 |Abar^H rbar|, 23 |A| (the Frobenius norm of the bidiagonal, capped by an estimate of |A|_2 so that it stays
+ * below |A|_F when the Lanczos vectors lose orthogonality), 24 cond(Abar), 25 the |x| the S1 test used, 26 alpha_1.  Systems with a non-zero
+ * stop code are frozen: their state is carried from slot to slot and nothing else of theirs is written.
+ * xk_lsmr_init: beta_1 = sqrt(sum Pb); uh <- b; slot k & 1 (alpha = 0); beta_1 = 0: stop code 1; run[s * 64] <- 1 / 0.
+ * xk_lsmr_bidiag: y <- Op / nu_x - (nu_x / nu_y) y, nu_x = sqrt(sum of the nblk_in partials Pin), nu_y = beta (half 0,
+ *   the u half) or alpha (half 1, the v half; 0: y is not read); Pout <- the nblk block partials of |y|^2; nu_x = 0: y
+ *   stays and the partials are 0.
+ * xk_lsmr_update: beta_{k+1} = sqrt(sum of the nblk_u partials Pu), alpha_{k+1} = sqrt(sum Pv); rotations; hbar <- h - c1
+ *   hbar, x <- x + c2 hbar, h <- vh / alpha_{k+1} - c3 h; Pxout <- partials of |x|^2 (Pxin: those of the step before);
+ *   estimates and stop code into slot (k + 1) & 1; run[s * 64] <- 1 while the system runs, else 0 (a one-partial
+ *   array for xk_kry_status with nblk = 1 and stop = 0.5).  On a start slot only h <- vh / alpha_1 and the state.
+ * XK_ERR_ARG, nothing launched: N <= 0, S < 0, k < 0, nblk (nblk_in, nblk_u) outside 1 .. 64, ld below N rounded up
+ *   to the 16 B vector, a NULL pointer, aliased vectors, damp < 0.  XK_ERR_UNSUPPORTED, nothing launched: a vector
+ *   pointer or a pitch that is not 16 B aligned. */
+int xk_lsmr_state_len(void);
+int xk_lsmr_init_f64(const double* b, double* uh, const double* Pb, double* state, double* run, int S, int N, long ld, int nblk,
+                     int k, void* stream);
+int xk_lsmr_bidiag_f64(const double* Op, double* y, const double* Pin, double* Pout, const double* state, int half, int S, int N,
+                       long ld, int nblk, int nblk_in, int k, void* stream);
+int xk_lsmr_update_f64(const double* vh, double* h, double* hbar, double* x, const double* Pu, const double* Pv, const double* Pxin, double* Pxout,
+                       double* state, double* run, int S, int N, long ld, int nblk, int nblk_u, int k, double damp,
+                       double atol, double btol, double conlim, void* stream);
+int xk_lsmr_init_f32(const float* b, float* uh, const float* Pb, double* state, float* run, int S, int N, long ld, int nblk,
+                     int k, void* stream);
+int xk_lsmr_bidiag_f32(const float* Op, float* y, const float* Pin, float* Pout, const double* state, int half, int S, int N,
+                       long ld, int nblk, int nblk_in, int k, void* stream);
+int xk_lsmr_update_f32(const float* vh, float* h, float* hbar, float* x, const float* Pu, const float* Pv, const float* Pxin, float* Pxout,
+                       double* state, float* run, int S, int N, long ld, int nblk, int nblk_u, int k, double damp,
+                       double atol, double btol, double conlim, void* stream);
+int xk_lsmr_init_c128(const double* b, double* uh, const double* Pb, double* state, double* run, int S, int N, long ld, int nblk,
+                     int k, void* stream);
+int xk_lsmr_bidiag_c128(const double* Op, double* y, const double* Pin, double* Pout, const double* state, int half, int S, int N,
+                       long ld, int nblk, int nblk_in, int k, void* stream);
+int xk_lsmr_update_c128(const double* vh, double* h, double* hbar, double* x, const double* Pu, const double* Pv, const double* Pxin, double* Pxout,
+                       double* state, double* run, int S, int N, long ld, int nblk, int nblk_u, int k, double damp,
+                       double atol, double btol, double conlim, void* stream);
+int xk_lsmr_init_c64(const float* b, float* uh, const float* Pb, double* state, float* run, int S, int N, long ld, int nblk,
+                     int k, void* stream);
+int xk_lsmr_bidiag_c64(const float* Op, float* y, const float* Pin, float* Pout, const double* state, int half, int S, int N,
+                       long ld, int nblk, int nblk_in, int k, void* stream);
+int xk_lsmr_update_c64(const float* vh, float* h, float* hbar, float* x, const float* Pu, const float* Pv, const float* Pxin, float* Pxout,
+                       double* state, float* run, int S, int N, long ld, int nblk, int nblk_u, int k, double damp,
+                       double atol, double btol, double conlim, void* stream);
+
 /* ---- device-side collectives of the sharded solvers (RCCL over xGMI) -------------------------
  * The per-iteration exchanges that reproduce the reference's GLOBAL decisions under batch sharding — MAX of
  * {max|resid|, flags} (xitorch/_impls/linalg/symeig.py:188-203), MAX of {max residual norm, unconverged flag}

@@ -152,6 +152,11 @@ def _declare(L):
         sigs["xk_minres_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
         sigs["xk_minres_lanczos_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, I, P])
         sigs["xk_minres_update_" + sfx] = (I, [P] * 7 + [I, P, P, I, I, Lg, I, I, P])
+    sigs["xk_lsmr_state_len"] = (I, [])
+    for sfx in ("f64", "f32", "c128", "c64"):
+        sigs["xk_lsmr_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
+        sigs["xk_lsmr_bidiag_" + sfx] = (I, [P] * 5 + [I, I, I, Lg, I, I, I, P])
+        sigs["xk_lsmr_update_" + sfx] = (I, [P] * 10 + [I, I, Lg, I, I, I, D, D, D, D, P])
     for sfx in ("f64", "f32", "c128", "c64"):
         sigs["xk_cheb_step_" + sfx] = (I, [P, Lg, Lg] * 4 + [P, I, I, I, P])
     sigs["xk_gkl_max_rows"] = (I, [])

@@ -668,6 +668,46 @@ def minres_update(v, y, w1, w2, x, Palpha, Pbeta, beta_is_dot, state, phi2, S, N
                                                     int(k), stream_ptr()), "xk_minres_update")
 
 
+# --------------------------------------------------------------------------- LSMR step kernels (xk_lsmr.hip)
+def lsmr_state(S, device):
+    """zeroed per-system scalar state of the LSMR kernels: (2 slots, S, xk_lsmr_state_len()) doubles"""
+    return torch.zeros((2, S, fn("xk_lsmr_state_len")()), dtype=torch.float64, device=device)
+
+
+def lsmr_init(b, uh, Pb, state, run, S, N, ld, nblk, k, raw=False):
+    """beta_1 = sqrt(sum Pb) from the |b|^2 partials, uh <- b, start state in slot k & 1, run <- 1 / 0 (b = 0)"""
+    require_device(uh, "vector")
+    rc = fn("xk_lsmr_init_" + suffix(uh.dtype))(ptr(b), ptr(uh), ptr(Pb), ptr(state), ptr(run), S, N, ld, nblk, int(k),
+                                                stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_lsmr_init")
+
+
+def lsmr_bidiag(Op, y, Pin, Pout, state, half, S, N, ld, nblk, nblk_in, k, raw=False):
+    """y <- Op / nu_x - (nu_x / nu_y) y: nu_x from the nblk_in partials Pin, nu_y from the state (half 0, the u half:
+    beta; half 1, the v half: alpha); Pout <- the nblk partials of |y|^2"""
+    require_device(y, "vector")
+    rc = fn("xk_lsmr_bidiag_" + suffix(y.dtype))(ptr(Op), ptr(y), ptr(Pin), ptr(Pout), ptr(state), int(half), S, N, ld,
+                                                 nblk, nblk_in, int(k), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_lsmr_bidiag")
+
+
+def lsmr_update(vh, h, hbar, x, Pu, Pv, Pxin, Pxout, state, run, S, N, ld, nblk, nblk_u, k, damp=0.0, atol=1e-6,
+                btol=1e-6, conlim=1e8, raw=False):
+    """step k of LSMR on the v side: the rotations, hbar, x and h in one pass, the estimates and the stop code into
+    state slot (k + 1) & 1, run <- 1 / 0, Pxout <- partials of |x|^2"""
+    require_device(x, "vector")
+    rc = fn("xk_lsmr_update_" + suffix(x.dtype))(ptr(vh), ptr(h), ptr(hbar), ptr(x), ptr(Pu), ptr(Pv), ptr(Pxin),
+                                                 ptr(Pxout), ptr(state), ptr(run), S, N, ld, nblk, nblk_u, int(k),
+                                                 float(damp), float(atol), float(btol), float(conlim), stream_ptr())
+    if raw:
+        return rc
+    check(rc, "xk_lsmr_update")
+
+
 # --------------------------------------------------------------------------- Chebyshev filter step (xk_cheb.hip)
 def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
     """out[b,c,:N] = coef[b,0] * AY[b,c,:N] + coef[b,1] * Y[b,c,:N] + coef[b,2] * Yprev[b,c,:N]  (xk_cheb_step_*): the
