@@ -61,7 +61,7 @@ def rounded_eps(eps, dtype):
 
 # ------------------------------------------------------------------------------------------------ block layout
 def block_range(N, nblk, blk, vn):
-    """replica of xk_krylov.hip block_range: element range [lo, hi) of block `blk` (in vn-element vectors)"""
+    """replica of block_range (xk_kry_layout.h): element range [lo, hi) of block `blk` (in vn-element vectors)"""
     chunks = (N + vn - 1) // vn
     per = (chunks + nblk - 1) // nblk
     lo, hi = blk * per * vn, (blk * per + per) * vn

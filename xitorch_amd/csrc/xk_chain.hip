@@ -20,6 +20,7 @@
 // Nothing here changes the arithmetic of the stages: same kernels / same formulas as the separate entry points
 // (the fused CholeskyQR sums its Gram entries per thread, then per wave, then across the 16 waves in fixed order).
 #include "xk_common.h"
+#include "xk_lane.h"
 
 extern "C" {
 long xk_dense_mm_workspace_elems(int B, int M, int N, int P, int trans);
@@ -80,17 +81,6 @@ static inline int transform_c(double* Tp, const double* W, int B, int P, int N, 
 }
 static inline int transform_c(float* Tp, const float* W, int B, int P, int N, long ldt, long sT, void* st) {
   return xk_panel_transform_f32(Tp, W, B, P, N, ldt, sT, st);
-}
-
-// a value every lane of the wave holds identically, moved to scalar registers (the 21 inverse-factor entries of the
-// fused CholeskyQR otherwise sit in VGPRs across its panel loop: with them the fp32 kernel spilled at 128 VGPRs)
-__device__ __forceinline__ float chain_uniform(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ double chain_uniform(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -407,7 +397,9 @@ __global__ __launch_bounds__(1024) void panel_cholqr_kernel(T* __restrict__ Tp, 
       for (int v = 0; v < VN; ++v) acc[v] = T(0);
 #pragma unroll
       for (int a = 0; a <= c; ++a) {
-        const T w = chain_uniform(Wsh[a][c]);                   // the same for every lane: lives in SGPRs
+        // the same for every lane: lives in SGPRs (the 21 inverse-factor entries otherwise sit in VGPRs across the
+        // panel loop: with them the fp32 kernel spilled at 128 VGPRs)
+        const T w = wave_uniform(Wsh[a][c]);
 #pragma unroll
         for (int v = 0; v < VN; ++v) acc[v] += w * t[a][v];
       }

@@ -31,19 +31,11 @@
 // arithmetic, one element per load.  The three coefficients of a row are wave-uniform (readfirstlane).  All stores are
 // ordinary vector-memory stores.
 #include "xk_common.h"
+#include "xk_lane.h"
 
 namespace xk {
 
 constexpr int CHEB_UNR = 4;                        // 16 B vectors per lane and array
-
-__device__ __forceinline__ float cheb_uniform(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ double cheb_uniform(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void cheb_step_kernel(
@@ -56,9 +48,9 @@ __global__ __launch_bounds__(256) void cheb_step_kernel(
   const int chunk = blockIdx.x - row * nchunk;
   const int b = row / p;
   const int c = row - b * p;
-  const T al = cheb_uniform((T)coef[3 * (long)b + 0]);
-  const T be = cheb_uniform((T)coef[3 * (long)b + 1]);
-  const T ga = cheb_uniform((T)coef[3 * (long)b + 2]);
+  const T al = wave_uniform((T)coef[3 * (long)b + 0]);
+  const T be = wave_uniform((T)coef[3 * (long)b + 1]);
+  const T ga = wave_uniform((T)coef[3 * (long)b + 2]);
   const bool prev = ga != T(0);                    // (-0.0 compares equal to 0: not read either)
   const T* a_ = AY + (long)b * sA + (long)c * ldA;
   const T* y_ = Y + (long)b * sY + (long)c * ldY;

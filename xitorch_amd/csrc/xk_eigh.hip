@@ -20,12 +20,10 @@
 // Accuracy: Jacobi is backward stable with small relative errors; convergence test
 // off(T)^2 <= (eps*k)^2 * ||T||_F^2 or a sweep without rotations.
 #include "xk_common.h"
+#include "xk_lane.h"
 
 namespace xk {
 
-template <typename T> struct Eps;
-template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-16; };
-template <> struct Eps<float> { static constexpr float v = 1.1920929e-07f; };
 
 template <typename T>
 __device__ __forceinline__ T block_sum_1024(T v, T* red) {
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(
     nrm += v * v;
   }
   nrm = block_sum_1024(nrm, red);
-  const T tol2 = (Eps<T>::v * k) * (Eps<T>::v * k) * nrm;
+  const T tol2 = (Limits<T>::eps * k) * (Limits<T>::eps * k) * nrm;
 
   // the 2x2 blocks (I, J) a thread updates are the same in every step: decode them once
   constexpr int MAXBLK = 4;                      // m*m <= 64*64 = 4096 blocks over 1024 threads
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(
         const T app = S[pp * ld + pp], aqq = S[qq * ld + qq];
         T c = T(1), s = T(0);
         // skip rotations that cannot change anything:  |apq| <= 0.01 eps sqrt(|app aqq|)   (compared squared)
-        const T thr2 = (Eps<T>::v * T(0.01)) * (Eps<T>::v * T(0.01)) * fabs(app * aqq);
+        const T thr2 = (Limits<T>::eps * T(0.01)) * (Limits<T>::eps * T(0.01)) * fabs(app * aqq);
         if (apq * apq > thr2 && apq != T(0)) {
           // the annihilating rotation without divisions: with d = aqq - app, e = 2 apq, h = hypot(d, e),
           // w = |d| + h:  tan = sign(d) e / w,  cos = sqrt(w / 2h) = w r,  sin = sign(d) e r,  r = rsqrt(2 h w)

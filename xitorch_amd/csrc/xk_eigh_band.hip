@@ -22,6 +22,7 @@
 // Nothing waits ACROSS workgroups: kernel boundaries are the only hand-offs between them (safe beside CU-masked streams);
 // the waves of the chase kernel's one workgroup per matrix wait on each other through LDS counters.
 #include "xk_common.h"
+#include "xk_lane.h"
 
 namespace xk {
 
@@ -30,25 +31,6 @@ constexpr int BAND_LP = BAND_NB + 1;             // LDS pitch of 16-column row b
 constexpr int BAND_LD = 2 * BAND_NB;             // diagonals kept per column of the band in the chase
 constexpr int BAND_STRIP = 64;                   // rows / columns of the trailing block per workgroup
 
-__device__ __forceinline__ double band_rl(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float band_rl(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double band_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float band_rcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  r = fmaf(fmaf(-x, r, 1.0f), r, r);
-  return r;
-}
 // sum over each 16-lane row, every lane of the row gets the (bit-identical) total; DPP only
 template <typename T>
 __device__ __forceinline__ T row16_sum(T v) {
@@ -57,17 +39,6 @@ __device__ __forceinline__ T row16_sum(T v) {
   v += lane_partner<2>(v);
   v += lane_partner<1>(v);
   return v;
-}
-// Householder reflector of x = (alpha, rest), sigma = |rest|^2: (I - tau v v^T) x = beta e1, v = (1, rest * scale)
-template <typename T>
-__device__ __forceinline__ void band_house(T alpha, T sigma, T& tau, T& beta, T& scale) {
-  tau = T(0); beta = alpha; scale = T(0);
-  if (!(sigma == T(0))) {                                   // (a NaN must poison the result, not be skipped)
-    const T nrm = sqrt(alpha * alpha + sigma);
-    beta = alpha >= T(0) ? -nrm : nrm;
-    tau = (beta - alpha) * band_rcp(beta);
-    scale = band_rcp(alpha - beta);
-  }
 }
 
 // number of panels of order n: panel j eliminates below the band in columns 16 j .. 16 j + 15 while >= 2 rows lie below
@@ -158,11 +129,11 @@ __global__ __launch_bounds__(1024) void band_qr_kernel(const T* __restrict__ Sws
       for (int u = 0; u < 16; u += 4) sacc += (rv[u] + rv[u + 1]) + (rv[u + 2] + rv[u + 3]);
       sacc = swap_add32(sacc, sacc);
       const T dot = swap_add16(sacc, sacc);             // every lane: the dot for its column c2
-      const T sigma = band_rl(dot, c);
+      const T sigma = readlane(dot, c);
       const T prow = Pl[c * LP + c2];                   // row c of the panel
-      const T alpha = band_rl(prow, c);
+      const T alpha = readlane(prow, c);
       T tau, beta, scale;
-      band_house(alpha, sigma, tau, beta, scale);
+      house(alpha, sigma, tau, beta, scale);
       if (lane < NB) {
         if (lane > c) tw[lane] = tau * (prow + scale * dot);
         if (lane < c) Tl[lane * NB + c] = (prow + scale * dot) * scal[lane];   // v_a^T v_c (v_a(c) = prow * scal[a])
@@ -217,7 +188,7 @@ __global__ __launch_bounds__(1024) void band_qr_kernel(const T* __restrict__ Sws
 #pragma unroll
       for (int a2 = 0; a2 < NB; ++a2) {
         if (a2 < c) {
-          const T za = band_rl(zc, a2);
+          const T za = readlane(zc, a2);
           t += trow[a2] * za;                               // trow[a2] = T[a][a2], zero for a2 < a
         }
       }
@@ -505,10 +476,10 @@ __device__ __forceinline__ void band_chase_step(T* __restrict__ Bw, const ChaseO
     e2[r] = Bw[o.e2[r]];
   }
   // ---- the reflector from the column before the window, rows of the window
-  const T sigma = band_rl(row16_sum(i16 >= 1 ? x * x : T(0)), 0);
-  const T alpha = band_rl(x, 0);
+  const T sigma = readlane(row16_sum(i16 >= 1 ? x * x : T(0)), 0);
+  const T alpha = readlane(x, 0);
   T tau, beta, scale;
-  band_house(alpha, sigma, tau, beta, scale);
+  house(alpha, sigma, tau, beta, scale);
   const T v = i16 == 0 ? T(1) : x * scale;                   // v by lane & 15
   T vr[4];                                                  // v by register row
 #pragma unroll

@@ -32,51 +32,13 @@
 // (8 -> 7.4 ms at 582).  Inside the Davidson pipeline the step kernels share the chip with the panel stream (64 CUs
 // left): 15.6 ms at order 582 there (scripts/s2_timeline.py).
 #include "xk_common.h"
+#include "xk_lane.h"
 #include "xk_tridiag.h"
 
 namespace xk {
 
-template <typename T> struct BigEps;
-template <> struct BigEps<double> { static constexpr double eps = 2.220446049250313e-16; static constexpr double tiny = 2.2250738585072014e-308; };
-template <> struct BigEps<float> { static constexpr float eps = 1.1920929e-07f; static constexpr float tiny = 1.17549435e-38f; };
-
 constexpr int BIG_MAXK = 1536;                            // (r06: was 1024; one launch per Householder step with 24 column slots)
 constexpr int BIG_MAXP = 256;                             // (r06: was 64; the LU batches and the finished vectors' rows in Y scale with p)
-
-__device__ __forceinline__ double big_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float big_readlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double big_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float big_rcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  r = fmaf(fmaf(-x, r, 1.0f), r, r);
-  return r;
-}
-// value of element r (0-based, wave-uniform) of a vector distributed as slot[t] of lane l <-> element l + 64 t
-template <typename T, int NT>
-__device__ __forceinline__ T dist_get(const T (&v)[NT], int r) {
-  const int t = r >> 6, l = r & 63;
-  T out = T(0);
-#pragma unroll
-  for (int u = 0; u < NT; ++u)
-    if (u == t) out = big_readlane(v[u], l);        // t is wave-uniform: a scalar branch per slot
-  return out;
-}
-
-__device__ __forceinline__ unsigned big_hash(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 
 template <typename T, int NT>
 __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
@@ -98,7 +60,7 @@ __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   T* S = Sws + (long)b * n * n;
   T* Yg = Y_out + (long)b * p * n;                    // (B, p, n): row j = eigenvector j, first of (d, e), then of T
-  const T eps = BigEps<T>::eps;
+  const T eps = Limits<T>::eps;
 
   {
     // the tridiagonalisation was done by the step kernels (tridiag_step_kernel below): (d, e, tau) wait in the aux block,
@@ -139,7 +101,7 @@ __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
   gu = wave_max(gu);
   emax = wave_max(emax);
   const T tnorm = fmax(fabs(gl), fabs(gu));
-  const T pivmin = BigEps<T>::tiny * fmax(T(1), emax);
+  const T pivmin = Limits<T>::tiny * fmax(T(1), emax);
   for (int w = wave; w < p; w += nw) {
     const int target = (uppest ? n - p + w : w) + 1;
     const T lamw = tri_bisect_wave<T>(dd, e2, n, target, gl, gu, tnorm, pivmin, eps, lane);   // (xk_tridiag.h)
@@ -184,7 +146,7 @@ __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
         const bool keep = fabs(dcur) >= fabs(li);       // no interchange
         T piv = keep ? dcur : li;
         if (keep && fabs(piv) < pfloor) piv = piv < T(0) ? -pfloor : pfloor;
-        const T inv = big_rcp(piv);
+        const T inv = rcp_nr(piv);
         const T fact = (keep ? li : dcur) * inv;
         const T up = keep ? ucur : dn;                  // row i of U: (1 / inv, up, up2)
         AT(dl, i) = fact; AT(dg, i) = inv; AT(du, i) = up; AT(du2, i) = keep ? T(0) : un; AT(sw, i) = keep ? T(0) : T(1);
@@ -206,10 +168,10 @@ __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
         for (; i + 1 < n; ++i) lu_row(i, ee[i], dd[i + 1] - shift, (i + 2 < n) ? ee[i + 1] : T(0));
       }
       if (fabs(dcur) < pfloor) dcur = dcur < T(0) ? -pfloor : pfloor;
-      AT(dg, n - 1) = big_rcp(dcur);
+      AT(dg, n - 1) = rcp_nr(dcur);
       T* z = Zb + (long)jl * n;
       for (int i = 0; i < n; ++i) {
-        const unsigned h = big_hash((unsigned)(i * 131 + j * 7919 + 12345));
+        const unsigned h = hash32((unsigned)(i * 131 + j * 7919 + 12345));
         z[i] = T((int)(h & 0xffffff) - 0x800000) / T(0x800000);
       }
     }
@@ -438,9 +400,9 @@ __global__ __launch_bounds__(512) void tridiag_eigh_big_kernel(
         T red3[4] = {da, db, cc, T(0)};
         wave_reduce_scatter<T, 4>(red3, lane);               // lane groups by bits 5, 4 hold the total of index 0 .. 3
         const T tot = red3[0];
-        da = big_readlane(tot, 0);                           // index = bit5 + 2 bit4 of the lane
-        db = big_readlane(tot, 32);
-        cc = big_readlane(tot, 16);
+        da = readlane(tot, 0);                           // index = bit5 + 2 bit4 of the lane
+        db = readlane(tot, 32);
+        cc = readlane(tot, 16);
         const T fa = ta * da;
         const T fb = tb * (db - fa * cc);
 #pragma unroll
@@ -567,13 +529,13 @@ __global__ __launch_bounds__(LB) void tridiag_step_kernel(
         if (!(t == 0 && lane == 0)) ss += x[t] * x[t];
       }
       const T sigma = wave_sum_dpp(ss);
-      const T alpha = big_readlane(x[0], 0);
+      const T alpha = readlane(x[0], 0);
       T tjw = T(0), scale = T(0), beta = alpha;
       if (!(sigma == T(0))) {                         // (a NaN row must poison the result, not be skipped)
         const T nrm = sqrt(alpha * alpha + sigma);
         beta = alpha >= T(0) ? -nrm : nrm;
-        tjw = (beta - alpha) * big_rcp(beta);
-        scale = big_rcp(alpha - beta);
+        tjw = (beta - alpha) * rcp_nr(beta);
+        scale = rcp_nr(alpha - beta);
       }
 #pragma unroll
       for (int t = 0; t < NT + 1; ++t) {
@@ -628,12 +590,12 @@ __global__ __launch_bounds__(LB) void tridiag_step_kernel(
     for (int t = 0; t < NT; ++t)
       if (!(t == 0 && lane == 0)) ss += a[t] * a[t];
     const T sigma = wave_sum_dpp(ss);
-    const T alpha = big_readlane(a[0], 0);
+    const T alpha = readlane(a[0], 0);
     T scale = T(0);
     if (!(sigma == T(0))) {
       const T nrm = sqrt(alpha * alpha + sigma);
       const T beta = alpha >= T(0) ? -nrm : nrm;
-      scale = big_rcp(alpha - beta);
+      scale = rcp_nr(alpha - beta);
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) vN[t] = (t == 0 && lane == 0) ? T(1) : a[t] * scale;

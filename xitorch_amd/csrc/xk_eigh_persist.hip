@@ -29,50 +29,10 @@
 // Outputs in the layout xk_eigh_big.hip's final kernel reads in mode 2: d, e, tau complete in the aux block, reflector r
 // parked in row r of the work copy S (columns > r + 1).
 #include "xk_common.h"
+#include "xk_lane.h"
 #include <type_traits>
 
 namespace xk {
-
-__device__ __forceinline__ double per_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float per_readlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double per_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float per_rcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  r = fmaf(fmaf(-x, r, 1.0f), r, r);
-  return r;
-}
-// element r (relative index, wave-uniform) of a vector distributed as slot[t] of lane l <-> element l + 64 t
-template <typename T, int NT>
-__device__ __forceinline__ T per_get(const T (&v)[NT], int r) {
-  const int t = r >> 6, l = r & 63;
-  T out = T(0);
-#pragma unroll
-  for (int u = 0; u < NT; ++u)
-    if (u == t) out = per_readlane(v[u], l);
-  return out;
-}
-// Householder reflector of x = (alpha, rest), sigma = |rest|^2: (I - tau v v^T) x = beta e1, v = (1, rest * scale)
-template <typename T>
-__device__ __forceinline__ void per_house(T alpha, T sigma, T& tau, T& beta, T& scale) {
-  tau = T(0); beta = alpha; scale = T(0);
-  if (!(sigma == T(0))) {                                   // (a NaN row must poison the result, not be skipped)
-    const T nrm = sqrt(alpha * alpha + sigma);
-    beta = alpha >= T(0) ? -nrm : nrm;
-    tau = (beta - alpha) * per_rcp(beta);
-    scale = per_rcp(alpha - beta);
-  }
-}
 
 constexpr int PER_NW = 8;                                   // waves per workgroup = row stride of a wave
 
@@ -148,9 +108,9 @@ __global__ __launch_bounds__(512) void tridiag_persist_kernel(
       if (!(t == 0 && lane == 0)) ss += x[t] * x[t];
     }
     const T sigma = wave_sum_dpp(ss);
-    const T alpha = per_readlane(x[0], 0);
+    const T alpha = readlane(x[0], 0);
     T beta, scale;
-    per_house(alpha, sigma, tj, beta, scale);
+    house(alpha, sigma, tj, beta, scale);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int c = base + lane + 64 * t;
@@ -206,7 +166,7 @@ __global__ __launch_bounds__(512) void tridiag_persist_kernel(
       const T K = T(0.5) * tj * tj * wave_sum_dpp(dot);     // w = tj A v;  K = tj/2 w.v
 #pragma unroll
       for (int t = 0; t < NT; ++t) q[t] = tj * wsum[t] - K * v[t];
-      q0 = per_get<T, NT>(q, r1);                           // v_j(j + 1) = 1
+      q0 = dist_get<T, NT>(q, r1);                          // v_j(j + 1) = 1
     }
     XK_PSTAMP(tA)
     // ---- B. row j + 1 after update j, reflector j + 1 ----------------------------------------------------------------
@@ -217,7 +177,7 @@ __global__ __launch_bounds__(512) void tridiag_persist_kernel(
         const int rc = lane + 64 * t;
         s1[t] = (64 * (t + 1) > r1 && rc >= r1) ? Srow[cur][rc] : T(0);
       }
-      const T sdiag = per_get<T, NT>(s1, r1);
+      const T sdiag = dist_get<T, NT>(s1, r1);
       T ss = T(0);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -227,9 +187,9 @@ __global__ __launch_bounds__(512) void tridiag_persist_kernel(
       }
       const T dnext = sdiag - T(2) * q0;
       const T sigma = wave_sum_dpp(ss);
-      const T alpha = per_get<T, NT>(a, r2);
+      const T alpha = dist_get<T, NT>(a, r2);
       T scaleN;
-      per_house(alpha, sigma, tauN, betaN, scaleN);
+      house(alpha, sigma, tauN, betaN, scaleN);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int rc = lane + 64 * t;

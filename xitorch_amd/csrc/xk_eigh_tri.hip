@@ -21,43 +21,12 @@
 //
 // Eigenvalues ascending, lowest / uppermost p selected exactly like `_take_eigpairs` (symeig.py:255-264).
 #include "xk_common.h"
+#include "xk_lane.h"
 #include "xk_tridiag.h"
 
 namespace xk {
 
-template <typename T> struct EpsT;
-template <> struct EpsT<double> { static constexpr double eps = 2.220446049250313e-16; static constexpr double tiny = 2.2250738585072014e-308; };
-template <> struct EpsT<float> { static constexpr float eps = 1.1920929e-07f; static constexpr float tiny = 1.17549435e-38f; };
-
 constexpr int TRI_MAXP = 16;
-
-// wave-uniform lane index -> v_readlane (scalar result, no LDS crossbar trip like a variable-index shuffle)
-__device__ __forceinline__ double readlane_t(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float readlane_t(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-// reciprocal to ~1-2 ulp: hardware estimate + Newton steps (a full IEEE division costs ~4x as much on the
-// sequential critical paths of the Sturm count and of the triangular solves)
-__device__ __forceinline__ double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float fast_rcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  r = fmaf(fmaf(-x, r, 1.0f), r, r);
-  return r;
-}
-
-__device__ __forceinline__ unsigned hash32(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
@@ -81,7 +50,7 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
   const int lane = tid & 63, nw = nt >> 6;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // provably wave-uniform (scalar row indices)
   const T* Tb = Tin + (long)b * sT;
-  const T eps = EpsT<T>::eps;
+  const T eps = Limits<T>::eps;
 
   // ---- load: lower triangle (eigh's UPLO = 'L') mirrored ---------------------------------------------
   for (int idx = tid; idx < n * n; idx += nt) {
@@ -105,13 +74,13 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
     const T x0 = c0 < n ? S[c0 * ld + j] : T(0);
     const T x1 = c1 < n ? S[c1 * ld + j] : T(0);
     const T sigma = wave_sum_dpp((lane > 0 ? x0 * x0 : T(0)) + x1 * x1);
-    const T alpha = readlane_t(x0, 0);
+    const T alpha = readlane(x0, 0);
     T tj = T(0), scale = T(0), beta = alpha;
     if (!(sigma == T(0))) {                           // (a NaN column must poison the result, not be skipped)
       const T nrm = sqrt(alpha * alpha + sigma);
       beta = alpha >= T(0) ? -nrm : nrm;
-      tj = (beta - alpha) * fast_rcp(beta);           // (every wave repeats this: keep it off the divider)
-      scale = fast_rcp(alpha - beta);
+      tj = (beta - alpha) * rcp_nr(beta);           // (every wave repeats this: keep it off the divider)
+      scale = rcp_nr(alpha - beta);
     }
     const T v0 = lane == 0 ? T(1) : x0 * scale;       // v over rows j+1.. (v[j+1] = 1)
     const T v1 = x1 * scale;
@@ -120,8 +89,8 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       int i = j + 1 + wave;
       for (; i + nw < n; i += 2 * nw) {               // two rows per trip: independent chains
         const int r0 = i - j - 1, r1 = r0 + nw;
-        const T vi0 = readlane_t(r0 < 64 ? v0 : v1, r0 & 63);
-        const T vi1 = readlane_t(r1 < 64 ? v0 : v1, r1 & 63);
+        const T vi0 = readlane(r0 < 64 ? v0 : v1, r0 & 63);
+        const T vi1 = readlane(r1 < 64 ? v0 : v1, r1 & 63);
         const T s00 = c0 < n ? S[i * ld + c0] : T(0), s01 = c1 < n ? S[i * ld + c1] : T(0);
         const T s10 = c0 < n ? S[(i + nw) * ld + c0] : T(0), s11 = c1 < n ? S[(i + nw) * ld + c1] : T(0);
         a0 += s00 * vi0; a1 += s01 * vi0;
@@ -129,7 +98,7 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       }
       if (i < n) {
         const int r0 = i - j - 1;
-        const T vi0 = readlane_t(r0 < 64 ? v0 : v1, r0 & 63);
+        const T vi0 = readlane(r0 < 64 ? v0 : v1, r0 & 63);
         a0 += (c0 < n ? S[i * ld + c0] : T(0)) * vi0;
         a1 += (c1 < n ? S[i * ld + c1] : T(0)) * vi0;
       }
@@ -149,8 +118,8 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       int i = j + 1 + wave;
       for (; i + nw < n; i += 2 * nw) {               // two rows per trip: their LDS round trips overlap
         const int r0 = i - j - 1, r1 = r0 + nw;
-        const T via = readlane_t(r0 < 64 ? v0 : v1, r0 & 63), qia = readlane_t(r0 < 64 ? q0 : q1, r0 & 63);
-        const T vib = readlane_t(r1 < 64 ? v0 : v1, r1 & 63), qib = readlane_t(r1 < 64 ? q0 : q1, r1 & 63);
+        const T via = readlane(r0 < 64 ? v0 : v1, r0 & 63), qia = readlane(r0 < 64 ? q0 : q1, r0 & 63);
+        const T vib = readlane(r1 < 64 ? v0 : v1, r1 & 63), qib = readlane(r1 < 64 ? q0 : q1, r1 & 63);
         T sa0 = T(0), sa1 = T(0), sb0 = T(0), sb1 = T(0);
         if (c0 < n) { sa0 = S[i * ld + c0]; sb0 = S[(i + nw) * ld + c0]; }
         if (c1 < n) { sa1 = S[i * ld + c1]; sb1 = S[(i + nw) * ld + c1]; }
@@ -159,8 +128,8 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       }
       if (i < n) {
         const int r0 = i - j - 1;
-        const T vi = readlane_t(r0 < 64 ? v0 : v1, r0 & 63);
-        const T qi = readlane_t(r0 < 64 ? q0 : q1, r0 & 63);
+        const T vi = readlane(r0 < 64 ? v0 : v1, r0 & 63);
+        const T qi = readlane(r0 < 64 ? q0 : q1, r0 & 63);
         if (c0 < n) S[i * ld + c0] -= vi * q0 + qi * v0;
         if (c1 < n) S[i * ld + c1] -= vi * q1 + qi * v1;
       }
@@ -196,7 +165,7 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
   gu = wave_max(gu);
   emax = wave_max(emax);
   const T tnorm = fmax(fabs(gl), fabs(gu));
-  const T pivmin = EpsT<T>::tiny * fmax(T(1), emax);
+  const T pivmin = Limits<T>::tiny * fmax(T(1), emax);
   for (int w = wave; w < p; w += nw) {
     const int target = (uppest ? n - p + w : w) + 1;       // smallest sigma with count(sigma) >= target
     const T lamw = tri_bisect_wave<T>(dd, e2, n, target, gl, gu, tnorm, pivmin, eps, lane);   // (xk_tridiag.h)
@@ -237,13 +206,13 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       const T un = (i + 2 < n) ? ee[i + 1] : T(0);
       if (fabs(dcur) >= fabs(li)) {
         if (fabs(dcur) < pfloor) dcur = dcur < T(0) ? -pfloor : pfloor;
-        const T inv = fast_rcp(dcur);
+        const T inv = rcp_nr(dcur);
         const T fact = li * inv;
         AT(dl, i) = fact; AT(dg, i) = inv; AT(du, i) = ucur; AT(du2, i) = T(0); AT(sw, i) = T(0);
         dcur = dn - fact * ucur;
         ucur = un;
       } else {
-        const T inv = fast_rcp(li);
+        const T inv = rcp_nr(li);
         const T fact = dcur * inv;
         AT(dl, i) = fact; AT(dg, i) = inv; AT(du, i) = dn; AT(du2, i) = un; AT(sw, i) = T(1);
         dcur = ucur - fact * dn;
@@ -251,7 +220,7 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
       }
     }
     if (fabs(dcur) < pfloor) dcur = dcur < T(0) ? -pfloor : pfloor;
-    AT(dg, n - 1) = fast_rcp(dcur);
+    AT(dg, n - 1) = rcp_nr(dcur);
     // start vector: deterministic pseudo-random in (-1, 1)
     T* z = Z + (long)j * n;
     for (int i = 0; i < n; ++i) {

@@ -17,10 +17,9 @@
 // (the rotation replay is a sequential recurrence of k steps), one wave per system in xk_gmres_solve (row i's dot
 // product over j > i is lane-parallel, y lives in LDS).
 #include "xk_common.h"
+#include "xk_kry_layout.h"
 
 namespace xk {
-
-constexpr int GMRES_PART = 64;     // pitch of the |r|^2 partial array shared with xk_kry_status
 
 template <typename T>
 __global__ __launch_bounds__(64) void gmres_step_kernel(
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(64) void gmres_step_kernel(
   const double gn = -t * gk;
   gs[k + 1] = gn;
   inv_hn[s] = hn > 0.0 ? (T)(1.0 / hn) : T(0);
-  est2[(long)s * GMRES_PART] = (T)(gn * gn);
+  est2[(long)s * KRY_MAX_PART] = (T)(gn * gn);
 }
 
 // q[k+1] = (w1 - sum_{j<=k} c2[j] q[j]) * inv_hn, in place in basis row k+1 (which holds w1).  Lane owns 16 B.

@@ -32,10 +32,10 @@
 // the tiles in a fixed order in double.  Loads are unconditional from clamped addresses; what a lane beyond the vector
 // loaded is multiplied by a zeroed w.
 #include "xk_common.h"
+#include "xk_kry_layout.h"
 
 namespace xk {
 
-constexpr int GMRESC_PART = 64;     // pitch of the |r|^2 partial array shared with xk_kry_status
 constexpr int GRAM_U = 4;           // 16 B vectors of w a lane keeps in registers
 constexpr int GRAM_ROWS = 64;       // basis rows between two cross-wave folds
 
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64) void gmres_step_c_kernel(
   gs[2 * (k + 1)] = hr;
   gs[2 * (k + 1) + 1] = hi;
   inv_hn[s] = hn > 0.0 ? (T)(1.0 / hn) : T(0);
-  est2[(long)s * GMRESC_PART] = (T)(hr * hr + hi * hi);
+  est2[(long)s * KRY_MAX_PART] = (T)(hr * hr + hi * hi);
 }
 
 // q[k+1] = (w1 - sum_{j<=k} c2[j] q[j]) * inv_hn, in place in basis row k+1 (which holds w1).  Lane owns 16 B.

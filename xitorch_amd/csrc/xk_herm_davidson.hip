@@ -16,13 +16,11 @@
 //                        CholeskyQR of a q-vector block in the (M-)inner product: G = W^H M W in a fixed summation
 //                        order, G (+ shift_rel trace G) = R^H R, W <- W R^-1 (and MW <- MW R^-1)
 #include "xk_common.h"
+#include "xk_complex.h"
+#include "xk_lane.h"
 #include "xk_tridiag.h"
 
 namespace xk {
-
-template <typename T> struct HermEps;
-template <> struct HermEps<double> { static constexpr double eps = 2.220446049250313e-16; static constexpr double tiny = 2.2250738585072014e-308; };
-template <> struct HermEps<float> { static constexpr float eps = 1.1920929e-07f; static constexpr float tiny = 1.17549435e-38f; };
 
 constexpr int HERM_MAXK = 128;      // order of the Rayleigh–Ritz matrix served by herm_eigh_kernel
 constexpr int HERM_MAXP = 16;       // wanted pairs per call
@@ -31,36 +29,6 @@ constexpr int HERM_RITZ_PC = 16;    // columns of Y per launch of herm_ritz_kern
 constexpr int HERM_CHOL_MAXQ = 32;  // block width of the CholeskyQR kernels
 constexpr int HERM_CHOL_CH = 32;    // vector elements per LDS chunk of the Gram kernel
 
-template <typename T> struct cx { T re, im; };
-template <typename T> __device__ __forceinline__ cx<T> cmul(cx<T> a, cx<T> b) {
-  return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
-}
-template <typename T> __device__ __forceinline__ cx<T> cmulc(cx<T> a, cx<T> b) {   // conj(a) b
-  return {a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re};
-}
-template <typename T> __device__ __forceinline__ void cfma(cx<T>& acc, cx<T> a, cx<T> b) {   // acc += a b
-  acc.re = fma(a.re, b.re, fma(-a.im, b.im, acc.re));
-  acc.im = fma(a.re, b.im, fma(a.im, b.re, acc.im));
-}
-template <typename T> __device__ __forceinline__ void cfmac(cx<T>& acc, cx<T> a, cx<T> b) {  // acc += conj(a) b
-  acc.re = fma(a.re, b.re, fma(a.im, b.im, acc.re));
-  acc.im = fma(a.re, b.im, fma(-a.im, b.re, acc.im));
-}
-template <typename T> __device__ __forceinline__ cx<T> cld(const T* p, long i) { return {p[2 * i], p[2 * i + 1]}; }
-template <typename T> __device__ __forceinline__ void cst(T* p, long i, cx<T> v) { p[2 * i] = v.re; p[2 * i + 1] = v.im; }
-
-__device__ __forceinline__ double herm_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float herm_readlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ unsigned herm_hash(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 __device__ __forceinline__ int pk(int i, int c) { return i * (i + 1) / 2 + c; }   // packed lower triangle, c <= i
 
 // bit pattern of a non-negative value widened to double: integer max over these is the max of the values, with a NaN
@@ -103,7 +71,7 @@ __global__ __launch_bounds__(HERM_THREADS) void herm_eigh_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const T* Tb = Tin + 2 * (long)b * sT;
   T* lu = ws + (long)b * 5 * n * p;
-  const T eps = HermEps<T>::eps;
+  const T eps = Limits<T>::eps;
 
   // (the diagonal is taken as real here, as zhetd2 does: an imaginary part handed over must not reach w = tau A22 v)
   for (int i = wave; i < n; i += nw)
@@ -125,7 +93,7 @@ __global__ __launch_bounds__(HERM_THREADS) void herm_eigh_kernel(
       const cx<T> x0 = i0 < n ? cld(S, pk(i0, j)) : cx<T>{T(0), T(0)};
       const cx<T> x1 = i1 < n ? cld(S, pk(i1, j)) : cx<T>{T(0), T(0)};
       const T sigma = wave_sum_dpp((lane > 0 ? x0.re * x0.re + x0.im * x0.im : T(0)) + x1.re * x1.re + x1.im * x1.im);
-      const T ar = herm_readlane(x0.re, 0), ai = herm_readlane(x0.im, 0);
+      const T ar = readlane(x0.re, 0), ai = readlane(x0.im, 0);
       cx<T> tj = {T(0), T(0)}, sc = {T(0), T(0)};
       T beta = ar;
       if (!(sigma == T(0) && ai == T(0))) {           // (a NaN column must poison the result, not be skipped)
@@ -218,7 +186,7 @@ __global__ __launch_bounds__(HERM_THREADS) void herm_eigh_kernel(
   gu = wave_max(gu);
   emax = wave_max(emax);
   const T tnorm = fmax(fabs(gl), fabs(gu));
-  const T pivmin = HermEps<T>::tiny * fmax(T(1), emax);
+  const T pivmin = Limits<T>::tiny * fmax(T(1), emax);
   for (int w = wave; w < p; w += nw) {
     const int target = (uppest ? n - p + w : w) + 1;
     const T lamw = tri_bisect_wave<T>(dd, e2, n, target, gl, gu, tnorm, pivmin, eps, lane);
@@ -266,7 +234,7 @@ __global__ __launch_bounds__(HERM_THREADS) void herm_eigh_kernel(
     AT(1, n - 1) = T(1) / dcur;
     T* z = Z + (long)j * n;
     for (int i = 0; i < n; ++i) {                     // deterministic pseudo-random start in (-1, 1)
-      const unsigned hh = herm_hash((unsigned)(i * 131 + j * 7919 + 12345));
+      const unsigned hh = hash32((unsigned)(i * 131 + j * 7919 + 12345));
       z[i] = T((int)(hh & 0xffffff) - 0x800000) / T(0x800000);
     }
   }

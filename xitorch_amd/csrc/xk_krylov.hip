@@ -17,48 +17,18 @@
 //   xk_kry_resid      r = b - y ; |r|^2, <r0,r>   (true-residual refresh, solve.py:148-149, 290-291)
 //   xk_kry_status     residual norms + global max + number of unconverged systems
 //
-// Reductions are two-stage and deterministic: producers write one partial per block,
-// consumers re-reduce the <= 64 partials of their system in a fixed order.  `_safedenom`
+// The block layout (prologue, loop, 16 B loads and stores, launch geometry) is defined in xk_kry_layout.h.
+// Reductions are two-stage and deterministic: producers write one partial per block (block_store_partial),
+// consumers re-reduce the <= 64 partials of their system in a fixed order (reduce_partials).  `_safedenom`
 // (solve.py:437-439: exact zeros become eps) is applied wherever the reference applies it.
 #include "xk_common.h"
+#include "xk_complex.h"
 #include "xk_kry_layout.h"
 
 namespace xk {
 
 template <typename T>
 __device__ __forceinline__ T safedenom(T v, T eps) { return v == T(0) ? eps : v; }
-
-// sum of the `nblk` partials of system s (all threads of the block get the value)
-template <typename T>
-__device__ __forceinline__ T reduce_partials(const T* __restrict__ part, int s, int nblk, T* sh) {
-  if (threadIdx.x < 64) {
-    T v = (int)threadIdx.x < nblk ? part[(long)s * KRY_MAX_PART + threadIdx.x] : T(0);
-    v = wave_sum(v);
-    if (threadIdx.x == 0) *sh = v;
-  }
-  __syncthreads();
-  const T r = *sh;
-  __syncthreads();
-  return r;
-}
-
-template <typename T>
-__device__ __forceinline__ void block_store_partial(T v, T* __restrict__ part, int s, int blk, T* sh4) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(long)s * KRY_MAX_PART + blk] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-  __syncthreads();
-}
-
-#define XK_KRY_PROLOGUE                                    \
-  typedef typename Vec16<T>::type VT;                      \
-  constexpr int VN = Vec16<T>::n;                          \
-  const int s = blockIdx.x / nblk;                         \
-  const int blk = blockIdx.x - s * nblk;                   \
-  int lo, hi;                                              \
-  block_range(N, nblk, blk, VN, lo, hi);                   \
-  const long base = (long)s * ld;
 
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -70,20 +40,20 @@ __global__ __launch_bounds__(256) void kry_dots_kernel(
   XK_KRY_PROLOGUE
   const T e = (E != nullptr) ? E[s] : T(0);
   T a1 = T(0), a2 = T(0);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT yv = *reinterpret_cast<const VT*>(y1 + base + j);
+  XK_KRY_LOOP {
+    VT yv = XK_KRY_LD(y1);
     if (E != nullptr) {
-      VT zv = *reinterpret_cast<const VT*>(shiftz + base + j);
+      VT zv = XK_KRY_LD(shiftz);
 #pragma unroll
       for (int v = 0; v < VN; ++v) yv[v] -= e * zv[v];
-      *reinterpret_cast<VT*>(y1 + base + j) = yv;
+      XK_KRY_ST(y1, yv);
     }
-    VT xv = y1_is_x1 ? yv : *reinterpret_cast<const VT*>(x1 + base + j);
+    VT xv = y1_is_x1 ? yv : XK_KRY_LD(x1);
 #pragma unroll
     for (int v = 0; v < VN; ++v) a1 += xv[v] * yv[v];
     if (P2 != nullptr) {
-      VT x2v = (x2 == y1) ? yv : *reinterpret_cast<const VT*>(x2 + base + j);
-      VT y2v = (y2 == y1) ? yv : *reinterpret_cast<const VT*>(y2 + base + j);
+      VT x2v = (x2 == y1) ? yv : XK_KRY_LD(x2);
+      VT y2v = (y2 == y1) ? yv : XK_KRY_LD(y2);
 #pragma unroll
       for (int v = 0; v < VN; ++v) a2 += x2v[v] * y2v[v];
     }
@@ -110,16 +80,16 @@ __global__ __launch_bounds__(256) void bicg_p_kernel(
     // reference first pass: rho_k = rho_knew, alpha = omega = 1, p = v = 0  -> beta irrelevant, p = r
     beta = T(0);
   }
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT rv = *reinterpret_cast<const VT*>(r + base + j);
+  XK_KRY_LOOP {
+    VT rv = XK_KRY_LD(r);
     VT o = rv;
     if (!first) {
-      VT pv = *reinterpret_cast<const VT*>(p + base + j);
-      VT vv = *reinterpret_cast<const VT*>(v + base + j);
+      VT pv = XK_KRY_LD(p);
+      VT vv = XK_KRY_LD(v);
 #pragma unroll
       for (int q = 0; q < VN; ++q) o[q] = rv[q] + beta * (pv[q] - om * vv[q]);
     }
-    *reinterpret_cast<VT*>(p + base + j) = o;
+    XK_KRY_ST(p, o);
   }
   if (blk == 0 && threadIdx.x == 0) rho_store[s] = rho_new;
 }
@@ -133,13 +103,13 @@ __global__ __launch_bounds__(256) void bicg_s_kernel(
   XK_KRY_PROLOGUE
   const T r0v = reduce_partials(Pr0v, s, nblk, &sh);
   const T alpha = rho[s] / safedenom(r0v, eps);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT rv = *reinterpret_cast<const VT*>(r + base + j);
-    VT vv = *reinterpret_cast<const VT*>(v + base + j);
+  XK_KRY_LOOP {
+    VT rv = XK_KRY_LD(r);
+    VT vv = XK_KRY_LD(v);
     VT o;
 #pragma unroll
     for (int q = 0; q < VN; ++q) o[q] = rv[q] - alpha * vv[q];
-    *reinterpret_cast<VT*>(sv + base + j) = o;
+    XK_KRY_ST(sv, o);
   }
   if (blk == 0 && threadIdx.x == 0) alpha_store[s] = alpha;
 }
@@ -161,18 +131,18 @@ __global__ __launch_bounds__(256) void bicg_final_kernel(
   const T omega = ts / safedenom(tt, eps);
   const T al = alpha[s];
   T arr = T(0), arho = T(0);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT xv = *reinterpret_cast<const VT*>(x + base + j);
-    VT yv = *reinterpret_cast<const VT*>(yd + base + j);
-    VT zv = *reinterpret_cast<const VT*>(zd + base + j);
+  XK_KRY_LOOP {
+    VT xv = XK_KRY_LD(x);
+    VT yv = XK_KRY_LD(yd);
+    VT zv = XK_KRY_LD(zd);
     VT o;
 #pragma unroll
     for (int q = 0; q < VN; ++q) o[q] = (xv[q] + al * yv[q]) + omega * zv[q];
-    *reinterpret_cast<VT*>(xout + base + j) = o;
+    XK_KRY_ST(xout, o);
     if (!skip_r) {
-      VT s2 = (sv == zd) ? zv : *reinterpret_cast<const VT*>(sv + base + j);
-      VT tv = *reinterpret_cast<const VT*>(t + base + j);
-      VT r0v = *reinterpret_cast<const VT*>(r0 + base + j);
+      VT s2 = (sv == zd) ? zv : XK_KRY_LD(sv);
+      VT tv = XK_KRY_LD(t);
+      VT r0v = XK_KRY_LD(r0);
       VT rn;
 #pragma unroll
       for (int q = 0; q < VN; ++q) {
@@ -180,7 +150,7 @@ __global__ __launch_bounds__(256) void bicg_final_kernel(
         arr += rn[q] * rn[q];
         arho += r0v[q] * rn[q];
       }
-      *reinterpret_cast<VT*>(r + base + j) = rn;
+      XK_KRY_ST(r, rn);
     }
   }
   if (!skip_r) {
@@ -198,18 +168,18 @@ __global__ __launch_bounds__(256) void kry_resid_kernel(
   __shared__ T sh4[4];
   XK_KRY_PROLOGUE
   T arr = T(0), arho = T(0);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT bv = *reinterpret_cast<const VT*>(b + base + j);
-    VT yv = *reinterpret_cast<const VT*>(y + base + j);
+  XK_KRY_LOOP {
+    VT bv = XK_KRY_LD(b);
+    VT yv = XK_KRY_LD(y);
     VT rn;
 #pragma unroll
     for (int q = 0; q < VN; ++q) { rn[q] = bv[q] - yv[q]; arr += rn[q] * rn[q]; }
     if (r0 != nullptr) {
-      VT r0v = *reinterpret_cast<const VT*>(r0 + base + j);
+      VT r0v = XK_KRY_LD(r0);
 #pragma unroll
       for (int q = 0; q < VN; ++q) arho += r0v[q] * rn[q];
     }
-    *reinterpret_cast<VT*>(r + base + j) = rn;
+    XK_KRY_ST(r, rn);
   }
   block_store_partial(arr, Prr, s, blk, sh4);
   if (Prho != nullptr) block_store_partial(r0 != nullptr ? arho : arr, Prho, s, blk, sh4);
@@ -228,19 +198,19 @@ __global__ __launch_bounds__(256) void cg_update_kernel(
   const T pap = reduce_partials(PpAp, s, nblk, &sh);
   const T alpha = rz / safedenom(pap, eps);
   T arr = T(0);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT xv = *reinterpret_cast<const VT*>(x + base + j);
-    VT pv = *reinterpret_cast<const VT*>(p + base + j);
+  XK_KRY_LOOP {
+    VT xv = XK_KRY_LD(x);
+    VT pv = XK_KRY_LD(p);
     VT o;
 #pragma unroll
     for (int q = 0; q < VN; ++q) o[q] = xv[q] + alpha * pv[q];
-    *reinterpret_cast<VT*>(xout + base + j) = o;
+    XK_KRY_ST(xout, o);
     if (!skip_r) {
-      VT rv = *reinterpret_cast<const VT*>(r + base + j);
-      VT av = *reinterpret_cast<const VT*>(Ap + base + j);
+      VT rv = XK_KRY_LD(r);
+      VT av = XK_KRY_LD(Ap);
 #pragma unroll
       for (int q = 0; q < VN; ++q) { rv[q] -= alpha * av[q]; arr += rv[q] * rv[q]; }
-      *reinterpret_cast<VT*>(r + base + j) = rv;
+      XK_KRY_ST(r, rv);
     }
   }
   if (!skip_r) block_store_partial(arr, Prr, s, blk, sh4);
@@ -256,12 +226,12 @@ __global__ __launch_bounds__(256) void cg_p_kernel(
   const T rzn = reduce_partials(Prz_new, s, nblk, &sh);
   const T rzo = reduce_partials(Prz_old, s, nblk, &sh);
   const T beta = rzn / safedenom(rzo, eps);
-  for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN) {
-    VT zv = *reinterpret_cast<const VT*>(z + base + j);
-    VT pv = *reinterpret_cast<const VT*>(p + base + j);
+  XK_KRY_LOOP {
+    VT zv = XK_KRY_LD(z);
+    VT pv = XK_KRY_LD(p);
 #pragma unroll
     for (int q = 0; q < VN; ++q) pv[q] = zv[q] + beta * pv[q];
-    *reinterpret_cast<VT*>(p + base + j) = pv;
+    XK_KRY_ST(p, pv);
   }
 }
 
@@ -306,18 +276,6 @@ __global__ __launch_bounds__(256) void kry_status_kernel(
 // (S, KRY_MAX_PART) layout, so xk_kry_status serves both families.  `_safedenom` (solve.py:437-439) replaces an
 // exact complex zero by eps + 0i.
 // ---------------------------------------------------------------------------------------------
-template <typename T> struct cx { T re, im; };
-template <typename T> __device__ __forceinline__ cx<T> cmul(cx<T> a, cx<T> b) {
-  return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
-}
-template <typename T> __device__ __forceinline__ cx<T> cdiv(cx<T> a, cx<T> b) {
-  const T d = b.re * b.re + b.im * b.im;
-  return {(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
-}
-template <typename T> __device__ __forceinline__ cx<T> csafe(cx<T> v, T eps) {
-  return (v.re == T(0) && v.im == T(0)) ? cx<T>{eps, T(0)} : v;
-}
-template <typename T> __device__ __forceinline__ cx<T> cload(const T* p, int s) { return {p[2 * (long)s], p[2 * (long)s + 1]}; }
 
 template <typename T>
 __device__ __forceinline__ cx<T> reduce_partials_c(const T* __restrict__ part, int s, int nblk, T* sh2) {
@@ -367,7 +325,7 @@ __global__ __launch_bounds__(256) void kry_dots_c_kernel(
     int N, long ld, int nblk, int y1_is_x1, int conj1) {
   __shared__ T sh8[8];
   XK_KRYC_PROLOGUE
-  const cx<T> e = (E != nullptr) ? cload(E, s) : cx<T>{T(0), T(0)};
+  const cx<T> e = (E != nullptr) ? cld(E, s) : cx<T>{T(0), T(0)};
   cx<T> a1 = {T(0), T(0)}, a2 = {T(0), T(0)};
   XK_CLOOP {
     VT yv = XK_LDV(y1);
@@ -412,8 +370,8 @@ __global__ __launch_bounds__(256) void bicg_p_c_kernel(
   const cx<T> rho_new = reduce_partials_c(Prho_new, s, nblk, sh2);
   cx<T> beta = {T(0), T(0)}, om = {T(0), T(0)};
   if (!first) {
-    om = csafe(cload(omega, s), eps);
-    beta = cmul(cdiv(rho_new, csafe(cload(rho_old, s), eps)), cdiv(cload(alpha, s), om));
+    om = csafe(cld(omega, s), eps);
+    beta = cmul(cdiv(rho_new, csafe(cld(rho_old, s), eps)), cdiv(cld(alpha, s), om));
   }
   XK_CLOOP {
     const VT rv = XK_LDV(r);
@@ -431,7 +389,7 @@ __global__ __launch_bounds__(256) void bicg_p_c_kernel(
     }
     XK_STV(p, o);
   }
-  if (blk == 0 && threadIdx.x == 0) { rho_store[2 * (long)s] = rho_new.re; rho_store[2 * (long)s + 1] = rho_new.im; }
+  if (blk == 0 && threadIdx.x == 0) cst(rho_store, s, rho_new);
 }
 
 template <typename T>
@@ -441,7 +399,7 @@ __global__ __launch_bounds__(256) void bicg_s_c_kernel(
   __shared__ T sh2[2];
   XK_KRYC_PROLOGUE
   const cx<T> r0v = reduce_partials_c(Pr0v, s, nblk, sh2);
-  const cx<T> al = cdiv(cload(rho, s), csafe(r0v, eps));
+  const cx<T> al = cdiv(cld(rho, s), csafe(r0v, eps));
   XK_CLOOP {
     const VT rv = XK_LDV(r);
     const VT vv = XK_LDV(v);
@@ -454,7 +412,7 @@ __global__ __launch_bounds__(256) void bicg_s_c_kernel(
     }
     XK_STV(sv, o);
   }
-  if (blk == 0 && threadIdx.x == 0) { alpha_store[2 * (long)s] = al.re; alpha_store[2 * (long)s + 1] = al.im; }
+  if (blk == 0 && threadIdx.x == 0) cst(alpha_store, s, al);
 }
 
 template <typename T>
@@ -471,7 +429,7 @@ __global__ __launch_bounds__(256) void bicg_final_c_kernel(
   const cx<T> ts = reduce_partials_c(Pts, s, nblk, sh2);
   const cx<T> tt = reduce_partials_c(Ptt, s, nblk, sh2);
   const cx<T> omega = cdiv(ts, csafe(tt, eps));
-  const cx<T> al = cload(alpha, s);
+  const cx<T> al = cld(alpha, s);
   T arr = T(0);
   cx<T> arho = {T(0), T(0)};
   XK_CLOOP {
@@ -508,7 +466,7 @@ __global__ __launch_bounds__(256) void bicg_final_c_kernel(
     block_store_partial(arr, Prr, s, blk, sh4);
     block_store_partial_c(arho, Prho, s, blk, sh8);
   }
-  if (blk == 0 && threadIdx.x == 0) { omega_store[2 * (long)s] = omega.re; omega_store[2 * (long)s + 1] = omega.im; }
+  if (blk == 0 && threadIdx.x == 0) cst(omega_store, s, omega);
 }
 
 template <typename T>
@@ -753,148 +711,147 @@ extern "C" {
 
 int xk_kry_max_partials(void) { return xk::KRY_MAX_PART; }
 
-#define XK_GRID(S, nblk) dim3((unsigned)((long)(S) * (nblk))), dim3(256), 0, (hipStream_t)stream
-#define XK_CHECK_KRY                                                     \
+#define XK_CHECK_KRY                                                            \
   if (S < 0 || N < 0 || nblk < 1 || nblk > xk::KRY_MAX_PART) return XK_ERR_ARG; \
   if (S == 0 || N == 0) return XK_OK;
 
-#define XK_DEFINE_KRY(SUF, T)                                                                             \
-  int xk_banded_mm_##SUF(const T* band, const T* X, T* Y, int B, int N, int hb, int C, long sBand,        \
-                         long ldx, long sX, long ldy, long sY, int trans, void* stream) {                 \
-    if (B < 0 || N < 0 || hb < 0 || C < 0) return XK_ERR_ARG;                                             \
-    if (B == 0 || N == 0 || C == 0) return XK_OK;                                                         \
-    return xk::banded_mm<T>(band, X, Y, B, N, hb, C, sBand, ldx, sX, ldy, sY, trans, (hipStream_t)stream); \
-  }                                                                                                       \
-  int xk_kry_dots_##SUF(const T* x1, T* y1, const T* x2, const T* y2, const T* shiftz, const T* E, T* P1, \
-                        T* P2, int S, int N, long ld, int nblk, void* stream) {                           \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::kry_dots_kernel<T>), XK_GRID(S, nblk), x1, y1, x2, y2, shiftz, E, P1, P2, N,   \
-                       ld, nblk, (x1 == y1) ? 1 : 0);                                                     \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_p_##SUF(const T* r, T* p, const T* v, const T* Prho_new, const T* rho_old, const T* alpha,  \
-                      const T* omega, T* rho_store, int S, int N, long ld, int nblk, double eps,          \
-                      int first, void* stream) {                                                          \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_p_kernel<T>), XK_GRID(S, nblk), r, p, v, Prho_new, rho_old, alpha,        \
-                       omega, rho_store, N, ld, nblk, (T)eps, first);                                     \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_s_##SUF(const T* r, const T* v, T* sv, const T* rho, const T* Pr0v, T* alpha_store, int S,   \
-                      int N, long ld, int nblk, double eps, void* stream) {                               \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_s_kernel<T>), XK_GRID(S, nblk), r, v, sv, rho, Pr0v, alpha_store, N, ld,  \
-                       nblk, (T)eps);                                                                     \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_final_##SUF(const T* x, T* xout, const T* yd, const T* zd, const T* sv, const T* t, T* r,    \
-                          const T* r0, const T* alpha, const T* Pts, const T* Ptt, T* omega_store,        \
-                          T* Prr, T* Prho, int S, int N, long ld, int nblk, double eps, int skip_r,       \
-                          void* stream) {                                                                 \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_final_kernel<T>), XK_GRID(S, nblk), x, xout, yd, zd, sv, t, r, r0,        \
-                       alpha, Pts, Ptt, omega_store, Prr, Prho, N, ld, nblk, (T)eps, skip_r);             \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_kry_resid_##SUF(const T* b, const T* y, T* r, const T* r0, T* Prr, T* Prho, int S, int N,         \
-                         long ld, int nblk, void* stream) {                                               \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::kry_resid_kernel<T>), XK_GRID(S, nblk), b, y, r, r0, Prr, Prho, N, ld, nblk);  \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_cg_update_##SUF(const T* x, T* xout, const T* p, const T* Ap, T* r, const T* Prz, const T* PpAp,  \
-                         T* Prr, int S, int N, long ld, int nblk, double eps, int skip_r, void* stream) { \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::cg_update_kernel<T>), XK_GRID(S, nblk), x, xout, p, Ap, r, Prz, PpAp, Prr, N,  \
-                       ld, nblk, (T)eps, skip_r);                                                         \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_cg_p_##SUF(const T* z, T* p, const T* Prz_new, const T* Prz_old, int S, int N, long ld,           \
-                    int nblk, double eps, void* stream) {                                                 \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::cg_p_kernel<T>), XK_GRID(S, nblk), z, p, Prz_new, Prz_old, N, ld, nblk,        \
-                       (T)eps);                                                                           \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_kry_status_##SUF(const T* Prr, const T* stop, T* rnorm, double* status, int S, int nblk,          \
-                          void* stream) {                                                                 \
-    if (S < 0 || nblk < 1 || nblk > xk::KRY_MAX_PART) return XK_ERR_ARG;                                   \
-    hipLaunchKernelGGL((xk::kry_status_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, Prr, stop,  \
-                       rnorm, status, S, nblk);                                                           \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
+#define XK_DEFINE_KRY(SUF, T)                                                                                 \
+  int xk_banded_mm_##SUF(const T* band, const T* X, T* Y, int B, int N, int hb, int C, long sBand,            \
+                         long ldx, long sX, long ldy, long sY, int trans, void* stream) {                     \
+    if (B < 0 || N < 0 || hb < 0 || C < 0) return XK_ERR_ARG;                                                 \
+    if (B == 0 || N == 0 || C == 0) return XK_OK;                                                             \
+    return xk::banded_mm<T>(band, X, Y, B, N, hb, C, sBand, ldx, sX, ldy, sY, trans, (hipStream_t)stream);    \
+  }                                                                                                           \
+  int xk_kry_dots_##SUF(const T* x1, T* y1, const T* x2, const T* y2, const T* shiftz, const T* E, T* P1,     \
+                        T* P2, int S, int N, long ld, int nblk, void* stream) {                               \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::kry_dots_kernel<T>), XK_KRY_GRID(S, nblk), x1, y1, x2, y2, shiftz, E, P1, P2, N,  \
+                       ld, nblk, (x1 == y1) ? 1 : 0);                                                         \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_bicg_p_##SUF(const T* r, T* p, const T* v, const T* Prho_new, const T* rho_old, const T* alpha,      \
+                      const T* omega, T* rho_store, int S, int N, long ld, int nblk, double eps,              \
+                      int first, void* stream) {                                                              \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::bicg_p_kernel<T>), XK_KRY_GRID(S, nblk), r, p, v, Prho_new, rho_old, alpha,       \
+                       omega, rho_store, N, ld, nblk, (T)eps, first);                                         \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_bicg_s_##SUF(const T* r, const T* v, T* sv, const T* rho, const T* Pr0v, T* alpha_store, int S,      \
+                      int N, long ld, int nblk, double eps, void* stream) {                                   \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::bicg_s_kernel<T>), XK_KRY_GRID(S, nblk), r, v, sv, rho, Pr0v, alpha_store, N, ld, \
+                       nblk, (T)eps);                                                                         \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_bicg_final_##SUF(const T* x, T* xout, const T* yd, const T* zd, const T* sv, const T* t, T* r,       \
+                          const T* r0, const T* alpha, const T* Pts, const T* Ptt, T* omega_store,            \
+                          T* Prr, T* Prho, int S, int N, long ld, int nblk, double eps, int skip_r,           \
+                          void* stream) {                                                                     \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::bicg_final_kernel<T>), XK_KRY_GRID(S, nblk), x, xout, yd, zd, sv, t, r, r0,       \
+                       alpha, Pts, Ptt, omega_store, Prr, Prho, N, ld, nblk, (T)eps, skip_r);                 \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_kry_resid_##SUF(const T* b, const T* y, T* r, const T* r0, T* Prr, T* Prho, int S, int N,            \
+                         long ld, int nblk, void* stream) {                                                   \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::kry_resid_kernel<T>), XK_KRY_GRID(S, nblk), b, y, r, r0, Prr, Prho, N, ld, nblk); \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_cg_update_##SUF(const T* x, T* xout, const T* p, const T* Ap, T* r, const T* Prz, const T* PpAp,     \
+                         T* Prr, int S, int N, long ld, int nblk, double eps, int skip_r, void* stream) {     \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::cg_update_kernel<T>), XK_KRY_GRID(S, nblk), x, xout, p, Ap, r, Prz, PpAp, Prr, N, \
+                       ld, nblk, (T)eps, skip_r);                                                             \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_cg_p_##SUF(const T* z, T* p, const T* Prz_new, const T* Prz_old, int S, int N, long ld,              \
+                    int nblk, double eps, void* stream) {                                                     \
+    XK_CHECK_KRY                                                                                              \
+    hipLaunchKernelGGL((xk::cg_p_kernel<T>), XK_KRY_GRID(S, nblk), z, p, Prz_new, Prz_old, N, ld, nblk,       \
+                       (T)eps);                                                                               \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
+  }                                                                                                           \
+  int xk_kry_status_##SUF(const T* Prr, const T* stop, T* rnorm, double* status, int S, int nblk,             \
+                          void* stream) {                                                                     \
+    if (S < 0 || nblk < 1 || nblk > xk::KRY_MAX_PART) return XK_ERR_ARG;                                      \
+    hipLaunchKernelGGL((xk::kry_status_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, Prr, stop,     \
+                       rnorm, status, S, nblk);                                                               \
+    XK_LAUNCH_CHECK();                                                                                        \
+    return XK_OK;                                                                                             \
   }
 
 XK_DEFINE_KRY(f64, double)
 XK_DEFINE_KRY(f32, float)
 
 // complex families: T* arguments point at interleaved (re, im) storage; N, ld in complex elements; eps real
-#define XK_DEFINE_KRYC(SUF, T)                                                                            \
-  int xk_kry_dots_##SUF(const T* x1, T* y1, const T* x2, const T* y2, const T* shiftz, const T* E, T* P1, \
-                        T* P2, int S, int N, long ld, int nblk, int conj1, void* stream) {                \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::kry_dots_c_kernel<T>), XK_GRID(S, nblk), x1, y1, x2, y2, shiftz, E, P1, P2, N, \
-                       ld, nblk, (x1 == y1) ? 1 : 0, conj1);                                              \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_p_##SUF(const T* r, T* p, const T* v, const T* Prho_new, const T* rho_old, const T* alpha,  \
-                      const T* omega, T* rho_store, int S, int N, long ld, int nblk, double eps,          \
-                      int first, void* stream) {                                                          \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_p_c_kernel<T>), XK_GRID(S, nblk), r, p, v, Prho_new, rho_old, alpha,      \
-                       omega, rho_store, N, ld, nblk, (T)eps, first);                                     \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_s_##SUF(const T* r, const T* v, T* sv, const T* rho, const T* Pr0v, T* alpha_store, int S,   \
-                      int N, long ld, int nblk, double eps, void* stream) {                               \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_s_c_kernel<T>), XK_GRID(S, nblk), r, v, sv, rho, Pr0v, alpha_store, N,    \
-                       ld, nblk, (T)eps);                                                                 \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_bicg_final_##SUF(const T* x, T* xout, const T* yd, const T* zd, const T* sv, const T* t, T* r,    \
-                          const T* r0, const T* alpha, const T* Pts, const T* Ptt, T* omega_store,        \
-                          T* Prr, T* Prho, int S, int N, long ld, int nblk, double eps, int skip_r,       \
-                          void* stream) {                                                                 \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::bicg_final_c_kernel<T>), XK_GRID(S, nblk), x, xout, yd, zd, sv, t, r, r0,      \
-                       alpha, Pts, Ptt, omega_store, Prr, Prho, N, ld, nblk, (T)eps, skip_r);             \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_kry_resid_##SUF(const T* b, const T* y, T* r, const T* r0, T* Prr, T* Prho, int S, int N,         \
-                         long ld, int nblk, void* stream) {                                               \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::kry_resid_c_kernel<T>), XK_GRID(S, nblk), b, y, r, r0, Prr, Prho, N, ld,       \
-                       nblk);                                                                             \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_cg_update_##SUF(const T* x, T* xout, const T* p, const T* Ap, T* r, const T* Prz, const T* PpAp,  \
-                         T* Prr, int S, int N, long ld, int nblk, double eps, int skip_r, void* stream) { \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::cg_update_c_kernel<T>), XK_GRID(S, nblk), x, xout, p, Ap, r, Prz, PpAp, Prr,   \
-                       N, ld, nblk, (T)eps, skip_r);                                                      \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
-  }                                                                                                       \
-  int xk_cg_p_##SUF(const T* z, T* p, const T* Prz_new, const T* Prz_old, int S, int N, long ld,           \
-                    int nblk, double eps, void* stream) {                                                 \
-    XK_CHECK_KRY                                                                                          \
-    hipLaunchKernelGGL((xk::cg_p_c_kernel<T>), XK_GRID(S, nblk), z, p, Prz_new, Prz_old, N, ld, nblk,      \
-                       (T)eps);                                                                           \
-    XK_LAUNCH_CHECK();                                                                                    \
-    return XK_OK;                                                                                         \
+#define XK_DEFINE_KRYC(SUF, T)                                                                                 \
+  int xk_kry_dots_##SUF(const T* x1, T* y1, const T* x2, const T* y2, const T* shiftz, const T* E, T* P1,      \
+                        T* P2, int S, int N, long ld, int nblk, int conj1, void* stream) {                     \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::kry_dots_c_kernel<T>), XK_KRY_GRID(S, nblk), x1, y1, x2, y2, shiftz, E, P1, P2, N, \
+                       ld, nblk, (x1 == y1) ? 1 : 0, conj1);                                                   \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_bicg_p_##SUF(const T* r, T* p, const T* v, const T* Prho_new, const T* rho_old, const T* alpha,       \
+                      const T* omega, T* rho_store, int S, int N, long ld, int nblk, double eps,               \
+                      int first, void* stream) {                                                               \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::bicg_p_c_kernel<T>), XK_KRY_GRID(S, nblk), r, p, v, Prho_new, rho_old, alpha,      \
+                       omega, rho_store, N, ld, nblk, (T)eps, first);                                          \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_bicg_s_##SUF(const T* r, const T* v, T* sv, const T* rho, const T* Pr0v, T* alpha_store, int S,       \
+                      int N, long ld, int nblk, double eps, void* stream) {                                    \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::bicg_s_c_kernel<T>), XK_KRY_GRID(S, nblk), r, v, sv, rho, Pr0v, alpha_store, N,    \
+                       ld, nblk, (T)eps);                                                                      \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_bicg_final_##SUF(const T* x, T* xout, const T* yd, const T* zd, const T* sv, const T* t, T* r,        \
+                          const T* r0, const T* alpha, const T* Pts, const T* Ptt, T* omega_store,             \
+                          T* Prr, T* Prho, int S, int N, long ld, int nblk, double eps, int skip_r,            \
+                          void* stream) {                                                                      \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::bicg_final_c_kernel<T>), XK_KRY_GRID(S, nblk), x, xout, yd, zd, sv, t, r, r0,      \
+                       alpha, Pts, Ptt, omega_store, Prr, Prho, N, ld, nblk, (T)eps, skip_r);                  \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_kry_resid_##SUF(const T* b, const T* y, T* r, const T* r0, T* Prr, T* Prho, int S, int N,             \
+                         long ld, int nblk, void* stream) {                                                    \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::kry_resid_c_kernel<T>), XK_KRY_GRID(S, nblk), b, y, r, r0, Prr, Prho, N, ld,       \
+                       nblk);                                                                                  \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_cg_update_##SUF(const T* x, T* xout, const T* p, const T* Ap, T* r, const T* Prz, const T* PpAp,      \
+                         T* Prr, int S, int N, long ld, int nblk, double eps, int skip_r, void* stream) {      \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::cg_update_c_kernel<T>), XK_KRY_GRID(S, nblk), x, xout, p, Ap, r, Prz, PpAp, Prr,   \
+                       N, ld, nblk, (T)eps, skip_r);                                                           \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_cg_p_##SUF(const T* z, T* p, const T* Prz_new, const T* Prz_old, int S, int N, long ld,               \
+                    int nblk, double eps, void* stream) {                                                      \
+    XK_CHECK_KRY                                                                                               \
+    hipLaunchKernelGGL((xk::cg_p_c_kernel<T>), XK_KRY_GRID(S, nblk), z, p, Prz_new, Prz_old, N, ld, nblk,      \
+                       (T)eps);                                                                                \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
   }
 
 XK_DEFINE_KRYC(c128, double)

@@ -5,10 +5,11 @@
 //     beta_{k+1} u_{k+1} = A v_k - alpha_k u_k,      alpha_{k+1} v_{k+1} = A^H u_{k+1} - beta_{k+1} v_k,
 // carried on the UN-normalised vectors uh_k = beta_k u_k and vh_k = alpha_k v_k (the norm is folded into the consumer,
 // as xk_minres.hip does: no scaling pass, and the host never reads a norm), two plane rotations per step (plus the
-// damping rotation) and the three-vector update of the paper's Algorithm.  The layout is that of xk_minres.hip: every
-// system (batch member x column) is one vector of a padded (S, ld) array, cut into nblk <= 64 blocks (block_range),
-// reductions are two-stage in a fixed order (one partial per block, the consumers re-reduce the partials of their
-// system in double), loads and stores are 16 B vectors, 256 threads, no atomics: repeated runs give identical bits.
+// damping rotation) and the three-vector update of the paper's Algorithm.  The layout is the one xk_kry_layout.h
+// defines (shared with xk_krylov.hip and xk_minres.hip): every system (batch member x column) is one vector of a padded
+// (S, ld) array, cut into nblk <= 64 blocks (block_range), reductions are two-stage in a fixed order (one partial per
+// block, the consumers re-reduce the partials of their system in double: reduce_partials_d), loads and stores are
+// 16 B vectors, 256 threads, no atomics: repeated runs give identical bits.
 //
 // Per-system scalar state, ALWAYS in double whatever the vector type, double-buffered: LS_NST doubles per system and
 // slot, state[(slot * S + s) * LS_NST + i]; a launch of step k reads slot k & 1 and xk_lsmr_update writes slot
@@ -50,6 +51,7 @@
 //                    run[s * 64] <- 1 (running) / 0 for xk_kry_status (nblk = 1, stop = 0.5)
 #include "xk_common.h"
 #include "xk_kry_layout.h"
+#include "xk_lane.h"
 
 namespace xk {
 
@@ -58,46 +60,12 @@ enum { LS_ALPHA = 0, LS_BETA, LS_ALPHABAR, LS_ZETABAR, LS_RHO, LS_RHOBAR, LS_CBA
        LS_BETAD, LS_RHODOLD, LS_TAUTILDEOLD, LS_THETATILDE, LS_D, LS_NORMA2, LS_MAXRBAR, LS_MINRBAR, LS_ITN, LS_FLAG,
        LS_NORMB, LS_NORMR, LS_NORMAR, LS_NORMA, LS_CONDA, LS_NORMX, LS_ALPHA1 };
 
-// sum, in double, of the `nblk` partials of system s (all threads of the block get the value)
-template <typename T>
-__device__ __forceinline__ double ls_reduce(const T* __restrict__ part, int s, int nblk, double* sh) {
-  if (threadIdx.x < 64) {
-    double v = (int)threadIdx.x < nblk ? (double)part[(long)s * KRY_MAX_PART + threadIdx.x] : 0.0;
-    v = wave_sum(v);
-    if (threadIdx.x == 0) *sh = v;
-  }
-  __syncthreads();
-  const double r = *sh;
-  __syncthreads();
-  return r;
-}
-
-// a block-uniform coefficient pinned to scalar registers
-__device__ __forceinline__ float ls_uniform(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ double ls_uniform(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
 __device__ __forceinline__ double ls_div(double a, double b) { return b == 0.0 ? 0.0 : a / b; }
 
-#define XK_LS_PROLOGUE                                     \
-  typedef typename Vec16<T>::type VT;                      \
-  constexpr int VN = Vec16<T>::n;                          \
-  const int s = blockIdx.x / nblk;                         \
-  const int blk = blockIdx.x - s * nblk;                   \
-  int lo, hi;                                              \
-  block_range(N, nblk, blk, VN, lo, hi);                   \
-  const long base = (long)s * ld;
-#define XK_LS_LOOP for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN)
-#define XK_LS_LD(p) (*reinterpret_cast<const VT*>((p) + base + j))
-#define XK_LS_LDNT(p) (ld_stream(reinterpret_cast<const VT*>((p) + base + j)))
-#define XK_LS_ST(p, val) (*reinterpret_cast<VT*>((p) + base + j) = (val))
-
-// block sum of the per-thread `acc`, written by thread 0 to dst (fixed order: wave butterflies, then four waves)
+// block sum of the per-thread `acc`, written by thread 0 to dst (fixed order: wave butterflies, then four waves).
+// block_partial of xk_kry_layout.h is the same sum; it forms the address of the partial in thread 0 alone, this one
+// takes it formed by every thread, and with the other the compiler allocates the registers of both kernels below
+// differently, so this form stays.
 template <typename T>
 __device__ __forceinline__ void ls_block_partial(T acc, T* sh4, T* dst) {
   acc = wave_sum(acc);
@@ -112,10 +80,10 @@ __global__ __launch_bounds__(256) void lsmr_init_kernel(
     const T* __restrict__ b, T* __restrict__ uh, const T* __restrict__ Pb, double* __restrict__ state,
     T* __restrict__ run, int S, int N, long ld, int nblk, int k) {
   __shared__ double sh;
-  XK_LS_PROLOGUE
-  const double bb = ls_reduce(Pb, s, nblk, &sh);
+  XK_KRY_PROLOGUE
+  const double bb = reduce_partials_d(Pb, s, nblk, 1, &sh);
   const double beta = sqrt(bb);                                           // (a NaN stays a NaN)
-  XK_LS_LOOP { XK_LS_ST(uh, XK_LS_LDNT(b)); }
+  XK_KRY_LOOP { XK_KRY_ST(uh, XK_KRY_LDNT(b)); }
   if (blk == 0 && threadIdx.x == 0) {
     double* st = state + ((long)(k & 1) * S + s) * LS_NST;
 #pragma unroll
@@ -135,36 +103,36 @@ __global__ __launch_bounds__(256) void lsmr_bidiag_kernel(
     const double* __restrict__ state, int half, int S, int N, long ld, int nblk, int nblk_in, int k) {
   __shared__ double sh;
   __shared__ T sh4[4];
-  XK_LS_PROLOGUE
+  XK_KRY_PROLOGUE
   const double* st = state + ((long)(k & 1) * S + s) * LS_NST;
   if (st[LS_FLAG] != 0.0) return;                      // frozen system: nothing is written (block-uniform)
-  const double nux = sqrt(ls_reduce(Pin, s, nblk_in, &sh));
+  const double nux = sqrt(reduce_partials_d(Pin, s, nblk_in, 1, &sh));
   const double nuy = half == 0 ? st[LS_BETA] : st[LS_ALPHA];
   T acc = T(0);
   if (nux == 0.0) {                                    // breakdown: y stays, |y|^2 = 0 tells the update
     if (threadIdx.x == 0) Pout[(long)s * KRY_MAX_PART + blk] = T(0);
     return;
   }
-  const T c0 = ls_uniform((T)(1.0 / nux));
+  const T c0 = wave_uniform((T)(1.0 / nux));
   if (nuy != 0.0) {
-    const T c1 = ls_uniform((T)(nux / nuy));
-    XK_LS_LOOP {
-      const VT ov = XK_LS_LDNT(Op);
-      VT yv = XK_LS_LD(y);
+    const T c1 = wave_uniform((T)(nux / nuy));
+    XK_KRY_LOOP {
+      const VT ov = XK_KRY_LDNT(Op);
+      VT yv = XK_KRY_LD(y);
 #pragma unroll
       for (int q = 0; q < VN; ++q) yv[q] = ov[q] * c0 - c1 * yv[q];
 #pragma unroll
       for (int q = 0; q < VN; ++q) acc += yv[q] * yv[q];
-      XK_LS_ST(y, yv);
+      XK_KRY_ST(y, yv);
     }
   } else {
-    XK_LS_LOOP {
-      VT yv = XK_LS_LDNT(Op);
+    XK_KRY_LOOP {
+      VT yv = XK_KRY_LDNT(Op);
 #pragma unroll
       for (int q = 0; q < VN; ++q) yv[q] = yv[q] * c0;
 #pragma unroll
       for (int q = 0; q < VN; ++q) acc += yv[q] * yv[q];
-      XK_LS_ST(y, yv);
+      XK_KRY_ST(y, yv);
     }
   }
   ls_block_partial(acc, sh4, Pout + (long)s * KRY_MAX_PART + blk);
@@ -179,7 +147,7 @@ __global__ __launch_bounds__(256) void lsmr_update_kernel(
     double damp, double atol, double btol, double conlim) {
   __shared__ double sh;
   __shared__ T sh4[4];
-  XK_LS_PROLOGUE
+  XK_KRY_PROLOGUE
   const double* st = state + ((long)(k & 1) * S + s) * LS_NST;
   double* so = state + ((long)((k + 1) & 1) * S + s) * LS_NST;
   const bool writer = blk == 0 && threadIdx.x == 0;
@@ -190,15 +158,15 @@ __global__ __launch_bounds__(256) void lsmr_update_kernel(
     }
     return;
   }
-  const double alpha = sqrt(ls_reduce(Pv, s, nblk, &sh));
+  const double alpha = sqrt(reduce_partials_d(Pv, s, nblk, 1, &sh));
   const double beta0 = st[LS_BETA];
   if (st[LS_ALPHA] == 0.0) {                           // start: alpha_1 = |A^H b| / beta_1, h = v_1; x, hbar stay
-    const T ia = ls_uniform(alpha == 0.0 ? T(0) : (T)(1.0 / alpha));
-    XK_LS_LOOP {
-      VT vv = XK_LS_LDNT(vh);
+    const T ia = wave_uniform(alpha == 0.0 ? T(0) : (T)(1.0 / alpha));
+    XK_KRY_LOOP {
+      VT vv = XK_KRY_LDNT(vh);
 #pragma unroll
       for (int q = 0; q < VN; ++q) vv[q] = vv[q] * ia;
-      XK_LS_ST(h, vv);
+      XK_KRY_ST(h, vv);
     }
     if (writer) {
 #pragma unroll
@@ -213,8 +181,8 @@ __global__ __launch_bounds__(256) void lsmr_update_kernel(
     }
     return;
   }
-  const double beta = sqrt(ls_reduce(Pu, s, nblk_u, &sh));
-  const double normx = sqrt(ls_reduce(Pxin, s, nblk, &sh));
+  const double beta = sqrt(reduce_partials_d(Pu, s, nblk_u, 1, &sh));
+  const double normx = sqrt(reduce_partials_d(Pxin, s, nblk, 1, &sh));
   // the damping rotation, then the two plane rotations of the Algorithm
   const double alphabar = st[LS_ALPHABAR], zetabar = st[LS_ZETABAR], rhoold = st[LS_RHO], rhobarold = st[LS_RHOBAR];
   const double cbar = st[LS_CBAR], sbar = st[LS_SBAR], zetaold = st[LS_ZETA];
@@ -227,16 +195,16 @@ __global__ __launch_bounds__(256) void lsmr_update_kernel(
   const double rhobar = sqrt(rhotemp * rhotemp + thetanew * thetanew);
   const double cbar_n = rhobar == 0.0 ? 1.0 : rhotemp / rhobar, sbar_n = ls_div(thetanew, rhobar);
   const double zeta = cbar_n * zetabar, zetabar_n = -sbar_n * zetabar;
-  const T c1 = ls_uniform((T)ls_div(thetabar * rho, rhoold * rhobarold));
-  const T c2 = ls_uniform((T)ls_div(zeta, rho * rhobar));
-  const T c3 = ls_uniform((T)ls_div(thetanew, rho));
-  const T ia = ls_uniform(alpha == 0.0 ? T(0) : (T)(1.0 / alpha));
+  const T c1 = wave_uniform((T)ls_div(thetabar * rho, rhoold * rhobarold));
+  const T c2 = wave_uniform((T)ls_div(zeta, rho * rhobar));
+  const T c3 = wave_uniform((T)ls_div(thetanew, rho));
+  const T ia = wave_uniform(alpha == 0.0 ? T(0) : (T)(1.0 / alpha));
   T acc = T(0);
-  XK_LS_LOOP {
-    const VT vv = XK_LS_LDNT(vh);
-    VT hv = XK_LS_LD(h);
-    VT hb = XK_LS_LD(hbar);
-    VT xv = XK_LS_LD(x);
+  XK_KRY_LOOP {
+    const VT vv = XK_KRY_LDNT(vh);
+    VT hv = XK_KRY_LD(h);
+    VT hb = XK_KRY_LD(hbar);
+    VT xv = XK_KRY_LD(x);
 #pragma unroll
     for (int q = 0; q < VN; ++q) {
       hb[q] = hv[q] - c1 * hb[q];
@@ -244,9 +212,9 @@ __global__ __launch_bounds__(256) void lsmr_update_kernel(
       hv[q] = vv[q] * ia - c3 * hv[q];
       acc += xv[q] * xv[q];
     }
-    XK_LS_ST(hbar, hb);
-    XK_LS_ST(x, xv);
-    XK_LS_ST(h, hv);
+    XK_KRY_ST(hbar, hb);
+    XK_KRY_ST(x, xv);
+    XK_KRY_ST(h, hv);
   }
   ls_block_partial(acc, sh4, Pxout + (long)s * KRY_MAX_PART + blk);
   if (writer) {
@@ -309,59 +277,58 @@ extern "C" {
 
 int xk_lsmr_state_len(void) { return xk::LS_NST; }
 
-#define XK_LS_GRID(S, nblk) dim3((unsigned)((long)(S) * (nblk))), dim3(256), 0, (hipStream_t)stream
-#define XK_LS_CHECK                                                                         \
-  {                                                                                         \
+#define XK_LS_CHECK                                                                                            \
+  {                                                                                                            \
     const int rc__ = xk::ls_check(S, (long)N * MUL, ld * MUL, nblk, k, (int)sizeof(T_), 16 / (int)sizeof(T_)); \
-    if (rc__ != XK_OK) return rc__;                                                         \
+    if (rc__ != XK_OK) return rc__;                                                                            \
   }
 
 // MUL = 1: real systems;  MUL = 2: interleaved complex ones (N, ld in complex elements)
-#define XK_DEFINE_LSMR(SUF, T, MUL_)                                                                          \
-  int xk_lsmr_init_##SUF(const T* b, T* uh, const T* Pb, double* state, T* run, int S, int N, long ld,        \
-                         int nblk, int k, void* stream) {                                                     \
-    typedef T T_;                                                                                             \
-    constexpr int MUL = MUL_;                                                                                 \
-    XK_LS_CHECK                                                                                               \
-    if (!b || !uh || !Pb || !state || !run) return XK_ERR_ARG;                                                \
-    if (xk::ls_misaligned(b) || xk::ls_misaligned(uh)) return XK_ERR_UNSUPPORTED;                             \
-    if (S == 0) return XK_OK;                                                                                 \
-    hipLaunchKernelGGL((xk::lsmr_init_kernel<T>), XK_LS_GRID(S, nblk), b, uh, Pb, state, run, S, N * MUL,     \
-                       ld * MUL, nblk, k);                                                                    \
-    XK_LAUNCH_CHECK();                                                                                        \
-    return XK_OK;                                                                                             \
-  }                                                                                                           \
-  int xk_lsmr_bidiag_##SUF(const T* Op, T* y, const T* Pin, T* Pout, const double* state, int half, int S,    \
-                           int N, long ld, int nblk, int nblk_in, int k, void* stream) {                      \
-    typedef T T_;                                                                                             \
-    constexpr int MUL = MUL_;                                                                                 \
-    XK_LS_CHECK                                                                                               \
-    if (nblk_in < 1 || nblk_in > xk::KRY_MAX_PART || half < 0 || half > 1) return XK_ERR_ARG;                 \
-    if (!Op || !y || !Pin || !Pout || !state || Pin == Pout || Op == y) return XK_ERR_ARG;                    \
-    if (xk::ls_misaligned(Op) || xk::ls_misaligned(y)) return XK_ERR_UNSUPPORTED;                             \
-    if (S == 0) return XK_OK;                                                                                 \
-    hipLaunchKernelGGL((xk::lsmr_bidiag_kernel<T>), XK_LS_GRID(S, nblk), Op, y, Pin, Pout, state, half, S,    \
-                       N * MUL, ld * MUL, nblk, nblk_in, k);                                                  \
-    XK_LAUNCH_CHECK();                                                                                        \
-    return XK_OK;                                                                                             \
-  }                                                                                                           \
-  int xk_lsmr_update_##SUF(const T* vh, T* h, T* hbar, T* x, const T* Pu, const T* Pv, const T* Pxin,         \
-                           T* Pxout, double* state, T* run, int S, int N, long ld, int nblk, int nblk_u,      \
-                           int k, double damp, double atol, double btol, double conlim, void* stream) {       \
-    typedef T T_;                                                                                             \
-    constexpr int MUL = MUL_;                                                                                 \
-    XK_LS_CHECK                                                                                               \
-    if (nblk_u < 1 || nblk_u > xk::KRY_MAX_PART || !(damp >= 0.0)) return XK_ERR_ARG;                         \
-    if (!vh || !h || !hbar || !x || !Pu || !Pv || !Pxin || !Pxout || !state || !run) return XK_ERR_ARG;       \
-    if (Pxin == Pxout || vh == h || vh == hbar || vh == x || h == hbar || h == x || hbar == x)                \
-      return XK_ERR_ARG;                                                                                      \
-    if (xk::ls_misaligned(vh) || xk::ls_misaligned(h) || xk::ls_misaligned(hbar) || xk::ls_misaligned(x))     \
-      return XK_ERR_UNSUPPORTED;                                                                              \
-    if (S == 0) return XK_OK;                                                                                 \
-    hipLaunchKernelGGL((xk::lsmr_update_kernel<T>), XK_LS_GRID(S, nblk), vh, h, hbar, x, Pu, Pv, Pxin, Pxout, \
-                       state, run, S, N * MUL, ld * MUL, nblk, nblk_u, k, damp, atol, btol, conlim);          \
-    XK_LAUNCH_CHECK();                                                                                        \
-    return XK_OK;                                                                                             \
+#define XK_DEFINE_LSMR(SUF, T, MUL_)                                                                           \
+  int xk_lsmr_init_##SUF(const T* b, T* uh, const T* Pb, double* state, T* run, int S, int N, long ld,         \
+                         int nblk, int k, void* stream) {                                                      \
+    typedef T T_;                                                                                              \
+    constexpr int MUL = MUL_;                                                                                  \
+    XK_LS_CHECK                                                                                                \
+    if (!b || !uh || !Pb || !state || !run) return XK_ERR_ARG;                                                 \
+    if (xk::ls_misaligned(b) || xk::ls_misaligned(uh)) return XK_ERR_UNSUPPORTED;                              \
+    if (S == 0) return XK_OK;                                                                                  \
+    hipLaunchKernelGGL((xk::lsmr_init_kernel<T>), XK_KRY_GRID(S, nblk), b, uh, Pb, state, run, S, N * MUL,     \
+                       ld * MUL, nblk, k);                                                                     \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_lsmr_bidiag_##SUF(const T* Op, T* y, const T* Pin, T* Pout, const double* state, int half, int S,     \
+                           int N, long ld, int nblk, int nblk_in, int k, void* stream) {                       \
+    typedef T T_;                                                                                              \
+    constexpr int MUL = MUL_;                                                                                  \
+    XK_LS_CHECK                                                                                                \
+    if (nblk_in < 1 || nblk_in > xk::KRY_MAX_PART || half < 0 || half > 1) return XK_ERR_ARG;                  \
+    if (!Op || !y || !Pin || !Pout || !state || Pin == Pout || Op == y) return XK_ERR_ARG;                     \
+    if (xk::ls_misaligned(Op) || xk::ls_misaligned(y)) return XK_ERR_UNSUPPORTED;                              \
+    if (S == 0) return XK_OK;                                                                                  \
+    hipLaunchKernelGGL((xk::lsmr_bidiag_kernel<T>), XK_KRY_GRID(S, nblk), Op, y, Pin, Pout, state, half, S,    \
+                       N * MUL, ld * MUL, nblk, nblk_in, k);                                                   \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
+  }                                                                                                            \
+  int xk_lsmr_update_##SUF(const T* vh, T* h, T* hbar, T* x, const T* Pu, const T* Pv, const T* Pxin,          \
+                           T* Pxout, double* state, T* run, int S, int N, long ld, int nblk, int nblk_u,       \
+                           int k, double damp, double atol, double btol, double conlim, void* stream) {        \
+    typedef T T_;                                                                                              \
+    constexpr int MUL = MUL_;                                                                                  \
+    XK_LS_CHECK                                                                                                \
+    if (nblk_u < 1 || nblk_u > xk::KRY_MAX_PART || !(damp >= 0.0)) return XK_ERR_ARG;                          \
+    if (!vh || !h || !hbar || !x || !Pu || !Pv || !Pxin || !Pxout || !state || !run) return XK_ERR_ARG;        \
+    if (Pxin == Pxout || vh == h || vh == hbar || vh == x || h == hbar || h == x || hbar == x)                 \
+      return XK_ERR_ARG;                                                                                       \
+    if (xk::ls_misaligned(vh) || xk::ls_misaligned(h) || xk::ls_misaligned(hbar) || xk::ls_misaligned(x))      \
+      return XK_ERR_UNSUPPORTED;                                                                               \
+    if (S == 0) return XK_OK;                                                                                  \
+    hipLaunchKernelGGL((xk::lsmr_update_kernel<T>), XK_KRY_GRID(S, nblk), vh, h, hbar, x, Pu, Pv, Pxin, Pxout, \
+                       state, run, S, N * MUL, ld * MUL, nblk, nblk_u, k, damp, atol, btol, conlim);           \
+    XK_LAUNCH_CHECK();                                                                                         \
+    return XK_OK;                                                                                              \
   }
 
 XK_DEFINE_LSMR(f64, double, 1)

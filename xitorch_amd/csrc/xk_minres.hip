@@ -2,10 +2,11 @@
 //
 // An extension (the reference has no MINRES): Lanczos tridiagonalisation of the (preconditioned) operator, one Givens
 // rotation per step to keep the tridiagonal's QR factors, and the three-term recurrence of the search directions
-// w_k = (v_k - eps_k w_{k-2} - delta_k w_{k-1}) / gamma_k that follows from  W R = V.  The layout is the one of
-// xk_krylov.hip: every system (batch member x column) is one length-N vector of a padded (S, ld) array, each system is
-// cut into nblk <= 64 blocks (block_range), reductions are two-stage in a fixed order (one partial per block, the
-// consumers re-reduce the partials of their system), loads and stores are 16 B vectors.
+// w_k = (v_k - eps_k w_{k-2} - delta_k w_{k-1}) / gamma_k that follows from  W R = V.  The layout is the one
+// xk_kry_layout.h defines (shared with xk_krylov.hip and xk_lsmr.hip): every system (batch member x column) is one
+// length-N vector of a padded (S, ld) array, each system is cut into nblk <= 64 blocks (block_range), reductions are
+// two-stage in a fixed order (one partial per block, the consumers re-reduce the partials of their system in double:
+// reduce_partials_d), loads and stores are 16 B vectors.
 //
 // Per-system scalar state, ALWAYS in double whatever the vector type, double-buffered: MR_NST doubles per system and
 // slot, state[(slot * S + s) * MR_NST + i]; a launch of iteration k reads slot k & 1 and (xk_minres_update only)
@@ -39,48 +40,22 @@ namespace xk {
 constexpr int MR_NST = 12;
 enum { MR_BETA = 0, MR_OLDB, MR_CS, MR_SN, MR_DBAR, MR_EPSLN, MR_PHIBAR, MR_FLAG, MR_ALPHA, MR_GAMMA, MR_DELTA, MR_PHI };
 
-// sum, in double, of the real parts of the `nblk` partials of system s (all threads of the block get the value)
-template <typename T>
-__device__ __forceinline__ double mr_reduce(const T* __restrict__ part, int s, int nblk, int pstride, double* sh) {
-  if (threadIdx.x < 64) {
-    double v = (int)threadIdx.x < nblk ? (double)part[((long)s * KRY_MAX_PART + threadIdx.x) * pstride] : 0.0;
-    v = wave_sum(v);
-    if (threadIdx.x == 0) *sh = v;
-  }
-  __syncthreads();
-  const double r = *sh;
-  __syncthreads();
-  return r;
-}
-
-#define XK_MR_PROLOGUE                                     \
-  typedef typename Vec16<T>::type VT;                      \
-  constexpr int VN = Vec16<T>::n;                          \
-  const int s = blockIdx.x / nblk;                         \
-  const int blk = blockIdx.x - s * nblk;                   \
-  int lo, hi;                                              \
-  block_range(N, nblk, blk, VN, lo, hi);                   \
-  const long base = (long)s * ld;
-#define XK_MR_LOOP for (int j = lo + threadIdx.x * VN; j < hi; j += 256 * VN)
-#define XK_MR_LD(p) (*reinterpret_cast<const VT*>((p) + base + j))
-#define XK_MR_ST(p, val) (*reinterpret_cast<VT*>((p) + base + j) = (val))
-
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void minres_init_kernel(
     const T* __restrict__ y0, T* __restrict__ v, const T* __restrict__ Pb, double* __restrict__ state,
     T* __restrict__ phi2, int S, int N, long ld, int nblk, int pstride, int k) {
   __shared__ double sh;
-  XK_MR_PROLOGUE
-  const double bb = mr_reduce(Pb, s, nblk, pstride, &sh);
+  XK_KRY_PROLOGUE
+  const double bb = reduce_partials_d(Pb, s, nblk, pstride, &sh);
   const double beta = bb > 0.0 ? sqrt(bb) : (bb < 0.0 ? 0.0 : bb);      // (a NaN stays a NaN)
   const double flag = bb < 0.0 ? 2.0 : (bb == 0.0 ? 1.0 : 0.0);
   const T sc = flag == 0.0 ? (T)(1.0 / beta) : T(0);
-  XK_MR_LOOP {
-    VT yv = XK_MR_LD(y0);
+  XK_KRY_LOOP {
+    VT yv = XK_KRY_LD(y0);
 #pragma unroll
     for (int q = 0; q < VN; ++q) yv[q] = flag == 0.0 ? yv[q] * sc : T(0);
-    XK_MR_ST(v, yv);
+    XK_KRY_ST(v, yv);
   }
   if (blk == 0 && threadIdx.x == 0) {
     double* st = state + ((long)(k & 1) * S + s) * MR_NST;
@@ -98,21 +73,21 @@ __global__ __launch_bounds__(256) void minres_lanczos_kernel(
     const double* __restrict__ state, T* __restrict__ Pbeta, int S, int N, long ld, int nblk, int pstride, int k) {
   __shared__ double sh;
   __shared__ T sh4[4];
-  XK_MR_PROLOGUE
+  XK_KRY_PROLOGUE
   const double* st = state + ((long)(k & 1) * S + s) * MR_NST;
   if (st[MR_FLAG] != 0.0) return;                      // frozen system: nothing is written (block-uniform)
-  const double alpha = mr_reduce(Palpha, s, nblk, pstride, &sh);
+  const double alpha = reduce_partials_d(Palpha, s, nblk, pstride, &sh);
   const double beta = st[MR_BETA], oldb = st[MR_OLDB];
   const T c2 = (T)(alpha / beta);
   const bool has1 = oldb != 0.0;
   const T c1 = has1 ? (T)(beta / oldb) : T(0);
   T acc = T(0);
-  XK_MR_LOOP {
-    const VT av = XK_MR_LD(Av);
-    const VT r2v = XK_MR_LD(r2);
+  XK_KRY_LOOP {
+    const VT av = XK_KRY_LD(Av);
+    const VT r2v = XK_KRY_LD(r2);
     VT y;
     if (has1) {
-      const VT r1v = XK_MR_LD(r1);
+      const VT r1v = XK_KRY_LD(r1);
 #pragma unroll
       for (int q = 0; q < VN; ++q) y[q] = (av[q] - c2 * r2v[q]) - c1 * r1v[q];
     } else {
@@ -121,14 +96,9 @@ __global__ __launch_bounds__(256) void minres_lanczos_kernel(
     }
 #pragma unroll
     for (int q = 0; q < VN; ++q) acc += y[q] * y[q];
-    XK_MR_ST(r1, y);
+    XK_KRY_ST(r1, y);
   }
-  if (Pbeta != nullptr) {
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) Pbeta[(long)s * KRY_MAX_PART + blk] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-  }
+  if (Pbeta != nullptr) block_partial(wave_sum(acc), Pbeta, s, blk, sh4);
 }
 
 // rotation + direction ring + solution + next Lanczos vector; y = r2 (no preconditioner) or P r2
@@ -138,7 +108,7 @@ __global__ __launch_bounds__(256) void minres_update_kernel(
     const T* __restrict__ Palpha, const T* __restrict__ Pbeta, double* __restrict__ state, T* __restrict__ phi2,
     int S, int N, long ld, int nblk, int pstride_a, int pstride_b, int k) {
   __shared__ double sh;
-  XK_MR_PROLOGUE
+  XK_KRY_PROLOGUE
   const double* st = state + ((long)(k & 1) * S + s) * MR_NST;
   double* so = state + ((long)((k + 1) & 1) * S + s) * MR_NST;
   const bool writer = blk == 0 && threadIdx.x == 0;
@@ -149,8 +119,8 @@ __global__ __launch_bounds__(256) void minres_update_kernel(
     }
     return;
   }
-  const double alpha = mr_reduce(Palpha, s, nblk, pstride_a, &sh);
-  const double bb = mr_reduce(Pbeta, s, nblk, pstride_b, &sh);
+  const double alpha = reduce_partials_d(Palpha, s, nblk, pstride_a, &sh);
+  const double bb = reduce_partials_d(Pbeta, s, nblk, pstride_b, &sh);
   const double beta = st[MR_BETA], cs = st[MR_CS], sn = st[MR_SN], dbar = st[MR_DBAR], phibar = st[MR_PHIBAR];
   const double oldeps = st[MR_EPSLN];
   if (bb < 0.0) {                                      // <r2, P r2> < 0: not a positive definite preconditioner
@@ -179,12 +149,12 @@ __global__ __launch_bounds__(256) void minres_update_kernel(
   const bool done = bnew == 0.0;                       // exact convergence: no division by a replaced zero
   const T te = (T)oldeps, td = (T)delta, tg = (T)(1.0 / gamma), tp = (T)phi;
   const T tb = done ? T(0) : (T)(1.0 / bnew);
-  XK_MR_LOOP {
-    VT vv = XK_MR_LD(v);
-    const VT w1v = XK_MR_LD(w1);
-    const VT w2v = XK_MR_LD(w2);
-    VT xv = XK_MR_LD(x);
-    const VT yv = XK_MR_LD(y);
+  XK_KRY_LOOP {
+    VT vv = XK_KRY_LD(v);
+    const VT w1v = XK_KRY_LD(w1);
+    const VT w2v = XK_KRY_LD(w2);
+    VT xv = XK_KRY_LD(x);
+    const VT yv = XK_KRY_LD(y);
     VT w;
 #pragma unroll
     for (int q = 0; q < VN; ++q) {
@@ -192,9 +162,9 @@ __global__ __launch_bounds__(256) void minres_update_kernel(
       xv[q] += tp * w[q];
       vv[q] = done ? T(0) : yv[q] * tb;
     }
-    XK_MR_ST(w1, w);
-    XK_MR_ST(x, xv);
-    XK_MR_ST(v, vv);
+    XK_KRY_ST(w1, w);
+    XK_KRY_ST(x, xv);
+    XK_KRY_ST(v, vv);
   }
   if (writer) {
     so[MR_BETA] = bnew;       so[MR_OLDB] = beta;        so[MR_CS] = csn;       so[MR_SN] = snn;
@@ -211,7 +181,6 @@ extern "C" {
 
 int xk_minres_state_len(void) { return xk::MR_NST; }
 
-#define XK_MR_GRID(S, nblk) dim3((unsigned)((long)(S) * (nblk))), dim3(256), 0, (hipStream_t)stream
 #define XK_MR_CHECK                                                                       \
   if (S < 0 || N < 0 || k < 0 || nblk < 1 || nblk > xk::KRY_MAX_PART) return XK_ERR_ARG;  \
   if (S == 0 || N == 0) return XK_OK;
@@ -221,7 +190,7 @@ int xk_minres_state_len(void) { return xk::MR_NST; }
   int xk_minres_init_##SUF(const T* y0, T* v, const T* Pb, double* state, T* phi2, int S, int N, long ld,   \
                            int nblk, int k, void* stream) {                                                 \
     XK_MR_CHECK                                                                                             \
-    hipLaunchKernelGGL((xk::minres_init_kernel<T>), XK_MR_GRID(S, nblk), y0, v, Pb, state, phi2, S,         \
+    hipLaunchKernelGGL((xk::minres_init_kernel<T>), XK_KRY_GRID(S, nblk), y0, v, Pb, state, phi2, S,        \
                        N * MUL, ld * MUL, nblk, PS, k);                                                     \
     XK_LAUNCH_CHECK();                                                                                      \
     return XK_OK;                                                                                           \
@@ -229,7 +198,7 @@ int xk_minres_state_len(void) { return xk::MR_NST; }
   int xk_minres_lanczos_##SUF(const T* Av, const T* r2, T* r1, const T* Palpha, const double* state,        \
                               T* Pbeta, int S, int N, long ld, int nblk, int k, void* stream) {             \
     XK_MR_CHECK                                                                                             \
-    hipLaunchKernelGGL((xk::minres_lanczos_kernel<T>), XK_MR_GRID(S, nblk), Av, r2, r1, Palpha, state,      \
+    hipLaunchKernelGGL((xk::minres_lanczos_kernel<T>), XK_KRY_GRID(S, nblk), Av, r2, r1, Palpha, state,     \
                        Pbeta, S, N * MUL, ld * MUL, nblk, PS, k);                                           \
     XK_LAUNCH_CHECK();                                                                                      \
     return XK_OK;                                                                                           \
@@ -238,7 +207,7 @@ int xk_minres_state_len(void) { return xk::MR_NST; }
                              int beta_is_dot, double* state, T* phi2, int S, int N, long ld, int nblk,      \
                              int k, void* stream) {                                                         \
     XK_MR_CHECK                                                                                             \
-    hipLaunchKernelGGL((xk::minres_update_kernel<T>), XK_MR_GRID(S, nblk), v, y, w1, w2, x, Palpha, Pbeta,  \
+    hipLaunchKernelGGL((xk::minres_update_kernel<T>), XK_KRY_GRID(S, nblk), v, y, w1, w2, x, Palpha, Pbeta, \
                        state, phi2, S, N * MUL, ld * MUL, nblk, PS, beta_is_dot ? PS : 1, k);               \
     XK_LAUNCH_CHECK();                                                                                      \
     return XK_OK;                                                                                           \

@@ -14,20 +14,10 @@
 // restarts from the Gershgorin interval in the ratio form.
 #pragma once
 #include "xk_common.h"
+#include "xk_lane.h"
 
 namespace xk {
 
-__device__ __forceinline__ double tri_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-__device__ __forceinline__ float tri_rcp(float x) {
-  float r = __builtin_amdgcn_rcpf(x);
-  r = fmaf(fmaf(-x, r, 1.0f), r, r);
-  return r;
-}
 __device__ __forceinline__ double tri_scale_down(double x, int e) { return ldexp(x, -e); }
 __device__ __forceinline__ float tri_scale_down(float x, int e) { return ldexpf(x, -e); }
 __device__ __forceinline__ int tri_exponent(double x) { return __builtin_amdgcn_frexp_exp(x); }
@@ -72,13 +62,13 @@ __device__ __forceinline__ int tri_sturm_ratio(const T* __restrict__ dd, const T
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      q = dc[u] - ec[u] * tri_rcp(q);
+      q = dc[u] - ec[u] * rcp_nr(q);
       if (fabs(q) < pivmin) q = -pivmin;
       cnt += q < T(0) ? 1 : 0;
     }
   }
   for (; i < n; ++i) {
-    q = dd[i] - sigma - e2[i - 1] * tri_rcp(q);
+    q = dd[i] - sigma - e2[i - 1] * rcp_nr(q);
     if (fabs(q) < pivmin) q = -pivmin;
     cnt += q < T(0) ? 1 : 0;
   }
