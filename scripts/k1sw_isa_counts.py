@@ -5,8 +5,9 @@ how many `s_waitcnt lgkmcnt(0)` / `vmcnt(0)` there are per MFMA and which vmcnt 
 import collections, json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "xitorch_amd", "csrc")
+INC = os.path.join(ROOT, "include")
 tmp = tempfile.mkdtemp()
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", SRC, "-c",
+subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", SRC, "-I", INC, "-c",
                        os.path.join(SRC, "xk_symmwide.hip"), "-save-temps", "-o", os.path.join(tmp, "x.o")], cwd=tmp)
 asm = open(os.path.join(tmp, "xk_symmwide-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
 kernels = {"r05 cooperative form (dense_symm_wide7_kernel<1,false>, opts 3)": "_ZN2xk23dense_symm_wide7_kernelILi1ELb0EE",

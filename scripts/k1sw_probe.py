@@ -6,10 +6,11 @@ import os, sys, json, subprocess, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "scripts", "_probe")
 SRC = os.path.join(ROOT, "xitorch_amd", "csrc")
+INC = os.path.join(ROOT, "include")
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     os.makedirs(OUT, exist_ok=True)
     for mode in (1, 2):
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", SRC,
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", SRC, "-I", INC,
                "-DXK_SW_PROBE=%d" % mode, os.path.join(SRC, "xk_symmwide.hip"), "-o", os.path.join(OUT, "k1sw_probe%d.so" % mode)]
         subprocess.check_call(cmd)
     sys.exit(0)

@@ -7,6 +7,7 @@ import os, sys, json, subprocess, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "scripts", "_probe")
 SRC = os.path.join(ROOT, "xitorch_amd", "csrc")
+INC = os.path.join(ROOT, "include")
 # trial builds of the r06 form (tile kernel only; never loaded by the package)
 VARIANTS = [("pitch272", ["-DXK_SW8_SWZ=0"]), ("prio", ["-DXK_SW8_PRIO=1"]), ("tr512", ["-DXK_SW_TR_BIG=512"]),
             ("tr2048", ["-DXK_SW_TR_BIG=2048"])]
@@ -16,7 +17,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
     builds = [("k1sw8_probe1.so", ["-DXK_SW8_PROBE=1"]), ("k1sw8_probe2.so", ["-DXK_SW8_PROBE=2"])]
     builds += [("k1sw8_var_%s.so" % name, flags) for name, flags in VARIANTS]
     for lib, flags in builds:
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", SRC] + flags + \
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", SRC, "-I", INC] + flags + \
               [os.path.join(SRC, "xk_symmwide.hip"), "-o", os.path.join(OUT, lib)]
         procs.append(subprocess.Popen(cmd))
     sys.exit(max(p.wait() for p in procs))

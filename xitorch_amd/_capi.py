@@ -53,144 +53,62 @@ def lib():
     return _lib
 
 
+_SCALARS = {"int": c_int, "unsigned": c_int, "unsigned int": c_int, "long": c_long, "double": c_double}
+_PROTOTYPE = re.compile(r"\b(int|long)\s+(xk_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+_signatures = None
+
+
+def _param_type(func, param):
+    if "*" in param:
+        return c_void_p
+    words = [w for w in param.split() if w != "const"]
+    if len(words) > 1 and words[-1] not in _SCALARS:
+        words.pop()                                   # the parameter's name
+    try:
+        return _SCALARS[" ".join(words)]
+    except KeyError:
+        raise NativeLibraryError("xitorch_amd: %s: parameter '%s' has no ctypes mapping (pointers, int, unsigned, "
+                                 "long and double cross the C ABI)" % (func, param)) from None
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every `int|long xk_name(params);` in the header text `text`.  Comments and
+    preprocessor lines are dropped first; a parameter is a pointer (anything with a `*`) -> c_void_p, `int` /
+    `unsigned` / `unsigned int` -> c_int, `long` -> c_long, `double` -> c_double, `(void)` -> no arguments.  Any other
+    spelling raises, and so does an `xk_name(` that is not part of a prototype of that shape: nothing goes unbound."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        params = " ".join(params.split())
+        args = [] if params == "void" else [_param_type(name, p.strip()) for p in params.split(",")]
+        sigs[name] = (_SCALARS[ret], args)
+    unparsed = sorted(set(re.findall(r"\b(xk_[a-z0-9_]+)\s*\(", text)) - set(sigs))
+    if unparsed:
+        raise NativeLibraryError("xitorch_amd: no prototype of the form `int|long xk_name(params);` understood for %s"
+                                 % ", ".join(unparsed))
+    return sigs
+
+
+def signatures():
+    """The prototypes of include/xitorch_amd.h (parsed once per process): the one place the bindings come from."""
+    global _signatures
+    if _signatures is None:
+        with open(HEADER_PATH) as f:
+            _signatures = parse_prototypes(f.read())
+    return _signatures
+
+
 def header_symbols():
     """All function names declared in include/xitorch_amd.h (used by the CPU tests)."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(xk_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(signatures())
 
 
 def _declare(L):
-    P, I, Lg, D = c_void_p, c_int, c_long, c_double
-    sigs = {
-        "xk_abi_version": (I, []),
-        "xk_stream_create_cu_masked": (I, [I, I, P]),
-        "xk_stream_create_cu_masked_pattern": (I, [I, I, I, P]),
-        "xk_probe_xcc": (I, [P, P, I, I, P]),
-        "xk_stream_destroy": (I, [P]),
-        "xk_stream_read": (I, [P, Lg, Lg, P, P]),
-        "xk_dense_mm_workspace_elems": (Lg, [I, I, I, I, I]),
-        "xk_dense_mm_f64": (I, [P, P, P, P, Lg, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, I, I, P]),
-        "xk_dense_mm_f32": (I, [P, P, P, P, Lg, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, I, I, P]),
-    }
-    for sfx in ("f64", "f32"):
-        sigs["xk_lincomb_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, Lg, D, D, P])
-        sigs["xk_ritz_residual_" + sfx] = (I, [P, P, P, P, P, P, P, I, I, I, I] + [Lg] * 12 + [P])
-        sigs["xk_panel_chol_" + sfx] = (I, [P, P, P, I, I, Lg, Lg, P])
-        sigs["xk_panel_transform_" + sfx] = (I, [P, P, I, I, I, Lg, Lg, P])
-        sigs["xk_diag_precond_" + sfx] = (I, [P, P, P, P, I, I, I, Lg, Lg, Lg, Lg, Lg, D, P])
-        sigs["xk_small_eigh_" + sfx] = (I, [P, P, P, P, Lg, P, I, I, I, I, I, Lg, Lg, P])
-    for sfx in ("f64", "f32"):
-        sigs["xk_davidson_ritz_" + sfx] = (I, [P] * 12 + [I, I, I, I] + [Lg] * 12 + [P, Lg, P, Lg, P])
-        sigs["xk_ritz_guard_" + sfx] = (I, [P, P, P, I, I, I, Lg, Lg, Lg, Lg, P, Lg, P, Lg, P])
-        sigs["xk_davidson_orth_" + sfx] = (I, [P, I, I, I, I, Lg, Lg, P, P, P, P, P, Lg, I, P])
-        sigs["xk_davidson_extend_t_" + sfx] = (I, [P, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, P, Lg, P])
-    sigs["xk_small_eigh_workspace_elems"] = (Lg, [I, I, I])
-    sigs["xk_small_eigh_tri_lds_bytes"] = (Lg, [I, I, I])
-    for sfx in ("f64", "f32"):
-        sigs["xk_small_eigh_tri_" + sfx] = (I, [P, P, P, P, I, I, I, I, Lg, Lg, I, P, P])
-    sigs["xk_small_eigh_big_batch"] = (I, [I, I, I])
-    sigs["xk_small_eigh_big_workspace_elems"] = (Lg, [I, I, I])
-    for sfx in ("f64", "f32"):
-        sigs["xk_small_eigh_big_" + sfx] = (I, [P, P, P, P, Lg, P, I, I, I, I, Lg, Lg, I, I, I, P])
-    sigs["xk_kry_max_partials"] = (I, [])
-    sigs["xk_csr_seg_len"] = (I, [])
-    sigs["xk_dense_symm_workspace_elems"] = (Lg, [I, I, I, I])
-    sigs["xk_dense_symm_wide_workspace_elems"] = (Lg, [I, I])
-    sigs["xk_dense_symm_wide_f32"] = (I, [P, P, P, P, Lg, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
-    sigs["xk_dense_symm_wide_tiles_f32"] = (I, [P, P, P, Lg, I, I, I, Lg, Lg, Lg, Lg, I, P])
-    sigs["xk_dense_symm_wide_fold_f32"] = (I, [P, P, Lg, I, I, I, Lg, Lg, I, P])
-    sigs["xk_dense_wide_workspace_elems"] = (Lg, [I, I, I, I, I])
-    sigs["xk_dense_wide_padded_width"] = (I, [I, I])
-    sigs["xk_dense_rows_wide_workspace_elems"] = (Lg, [I, I, I, I, I])
-    for sfx in ("f64", "f32"):
-        sigs["xk_dense_rows_wide_" + sfx] = (I, [P, P, P, P, Lg, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, P])
-    for sfx in ("f64", "f32"):
-        sigs["xk_dense_wide_" + sfx] = (I, [P, P, P, P, Lg, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, P])
-    for sfx in ("f64", "f32"):
-        sigs["xk_group_status_" + sfx] = (I, [P, P, P, P, P, I, P])
-        sigs["xk_dense_symm_" + sfx] = (I, [P, P, P, P, Lg, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_dense_symm_tiles_" + sfx] = (I, [P, P, P, Lg, I, I, I, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_dense_symm_fold_" + sfx] = (I, [P, P, Lg, I, I, I, Lg, Lg, I, P])
-    for sfx in ("f64", "f32"):
-        sigs["xk_banded_mm_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_kry_dots_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, P])
-        sigs["xk_bicg_p_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
-        sigs["xk_bicg_s_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, D, P])
-        sigs["xk_bicg_final_" + sfx] = (I, [P] * 14 + [I, I, Lg, I, D, I, P])
-        sigs["xk_kry_resid_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, P])
-        sigs["xk_cg_update_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
-        sigs["xk_cg_p_" + sfx] = (I, [P] * 4 + [I, I, Lg, I, D, P])
-        sigs["xk_kry_status_" + sfx] = (I, [P] * 4 + [I, I, P])
-        sigs["xk_banded_grad_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_dense_outer_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_csr_mm_" + sfx] = (I, [P, P, P, P, Lg, P, P, P, P, I, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, P])
-        sigs["xk_csr_sddmm_" + sfx] = (I, [P, P, P, P, P, I, I, I, I, I, Lg, Lg, Lg, Lg, Lg, P])
-    for sfx in ("c128", "c64"):
-        sigs["xk_csr_mm_" + sfx] = (I, [P, P, P, P, Lg, P, P, P, P, I, P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_csr_sddmm_" + sfx] = (I, [P, P, P, P, P, I, I, I, I, I, Lg, Lg, Lg, Lg, Lg, P])
-    for sfx in ("f64", "f32"):
-        sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
-        sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])
-        sigs["xk_gmres_solve_" + sfx] = (I, [P, P, P, Lg, I, I, I, P])
-    for sfx in ("c128", "c64"):
-        sigs["xk_gmres_gram_" + sfx] = (I, [P, P, P, P, I, I, I, Lg, Lg, Lg, Lg, I, P])
-        sigs["xk_lincomb_" + sfx] = (I, [P, P, P, I, I, I, I, Lg, Lg, Lg, Lg, Lg, Lg, D, D, P])
-        sigs["xk_gmres_step_" + sfx] = (I, [P, Lg, P, Lg, I, I, P, P, P, P, P, P, I, P])
-        sigs["xk_gmres_finish_" + sfx] = (I, [P, P, Lg, P, I, I, I, Lg, Lg, P])
-        sigs["xk_gmres_solve_" + sfx] = (I, [P, P, P, Lg, I, I, I, P])
-    for sfx in ("c64", "c128"):
-        sigs["xk_kry_dots_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, I, P])
-        sigs["xk_bicg_p_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
-        sigs["xk_bicg_s_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, D, P])
-        sigs["xk_bicg_final_" + sfx] = (I, [P] * 14 + [I, I, Lg, I, D, I, P])
-        sigs["xk_kry_resid_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, P])
-        sigs["xk_cg_update_" + sfx] = (I, [P] * 8 + [I, I, Lg, I, D, I, P])
-        sigs["xk_cg_p_" + sfx] = (I, [P] * 4 + [I, I, Lg, I, D, P])
-    sigs["xk_minres_state_len"] = (I, [])
-    for sfx in ("f64", "f32", "c128", "c64"):
-        sigs["xk_minres_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
-        sigs["xk_minres_lanczos_" + sfx] = (I, [P] * 6 + [I, I, Lg, I, I, P])
-        sigs["xk_minres_update_" + sfx] = (I, [P] * 7 + [I, P, P, I, I, Lg, I, I, P])
-    sigs["xk_lsmr_state_len"] = (I, [])
-    for sfx in ("f64", "f32", "c128", "c64"):
-        sigs["xk_lsmr_init_" + sfx] = (I, [P] * 5 + [I, I, Lg, I, I, P])
-        sigs["xk_lsmr_bidiag_" + sfx] = (I, [P] * 5 + [I, I, I, Lg, I, I, I, P])
-        sigs["xk_lsmr_update_" + sfx] = (I, [P] * 10 + [I, I, Lg, I, I, I, D, D, D, D, P])
-    for sfx in ("f64", "f32", "c128", "c64"):
-        sigs["xk_cheb_step_" + sfx] = (I, [P, Lg, Lg] * 4 + [P, I, I, I, P])
-    sigs["xk_gkl_max_rows"] = (I, [])
-    sigs["xk_gkl_bsvd_max"] = (I, [])
-    sigs["xk_gkl_chunk_elems"] = (I, [I])
-    for sfx in ("f64", "f32", "c128", "c64"):
-        sigs["xk_gkl_sweep_" + sfx] = (I, [P, Lg, Lg, P, Lg, P, Lg, P, Lg, P, P, Lg, I, I, I, P])
-    sigs["xk_gkl_finish"] = (I, [P, I, I, I, P, Lg, P, P, P, Lg, P, D, P, I, P])
-    sigs["xk_gkl_bsvd"] = (I, [P, P, P, P, I, I, I, I, I, D, P, P, P, P, P, P, P])
-    sigs["xk_fsai_max_row"] = (I, [])
-    for sfx in ("f64", "f32", "c128", "c64"):
-        sigs["xk_fsai_build_" + sfx] = (I, [P, P, P, Lg, I, P, P, P, Lg, I, P, I, I, P])
-    sigs["xk_herm_eigh_lds_bytes"] = (Lg, [I, I, I])
-    sigs["xk_herm_eigh_workspace_elems"] = (Lg, [I, I, I])
-    for sfx in ("c128", "c64"):
-        sigs["xk_herm_eigh_" + sfx] = (I, [P, P, P, P, P, Lg, I, I, I, I, Lg, Lg, P])
-        sigs["xk_herm_ritz_" + sfx] = (I, [P] * 8 + [I, I, I, I] + [Lg] * 14 + [P])
-        sigs["xk_herm_cholqr_" + sfx] = (I, [P, P, P, P, I, I, I, Lg, Lg, Lg, Lg, D, P])
-    sigs["xk_comm_available"] = (I, [])
-    sigs["xk_comm_unique_id"] = (I, [P])
-    sigs["xk_comm_init_rank"] = (I, [P, I, I, I, P])
-    sigs["xk_comm_init_all"] = (I, [I, P, P])
-    sigs["xk_comm_size"] = (I, [P, P, P])
-    sigs["xk_comm_destroy"] = (I, [P])
-    sigs["xk_allreduce_f64"] = (I, [P, P, Lg, I, P])
-    sigs["xk_allreduce_f32"] = (I, [P, P, Lg, I, P])
-    sigs["xk_vec_dots_workspace_elems"] = (Lg, [])
-    for sfx in ("f64", "f32"):
-        sigs["xk_vec_dots_" + sfx] = (I, [P] * 8 + [I, Lg, P, Lg, P, P])
-        sigs["xk_broyden_axpy_" + sfx] = (I, [P, P, D, P, D, P, Lg, P, P, I, D, Lg, P])
-    for name, (res, args) in sigs.items():
-        if not hasattr(L, name):
-            continue  # reported by the symbol test, and by check() at call time
-        f = getattr(L, name)
+    for name, (res, args) in signatures().items():
+        f = getattr(L, name, None)
+        if f is None:
+            continue  # reported by the symbol test, and by fn() at call time
         f.restype = res
         f.argtypes = args
 
@@ -210,16 +128,14 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
+_SUFFIX = {torch.float64: "f64", torch.float32: "f32", torch.complex128: "c128", torch.complex64: "c64"}
+
+
 def suffix(dtype):
-    if dtype == torch.float64:
-        return "f64"
-    if dtype == torch.float32:
-        return "f32"
-    if dtype == torch.complex128:
-        return "c128"
-    if dtype == torch.complex64:
-        return "c64"
-    raise NativeLibraryError("xitorch_amd native kernels support float64/float32, got %s" % dtype)
+    try:
+        return _SUFFIX[dtype]
+    except KeyError:
+        raise NativeLibraryError("xitorch_amd native kernels support float64/float32, got %s" % dtype) from None
 
 
 def require_device(t, what="tensor"):
@@ -234,3 +150,14 @@ def fn(name):
     if not hasattr(L, name):
         raise NativeLibraryError("xitorch_amd: symbol %s missing from %s" % (name, LIB_PATH))
     return getattr(L, name)
+
+
+def call(base, dtype, *args, raw=False, what=None):
+    """The one way from Python into a stream-ordered entry point: `base` + "_" + the suffix of `dtype` (None: an
+    entry point without a type suffix) is called with `args` -- explicit `ptr(...)`, int and float values, converted by
+    the header's argtypes -- and the current HIP stream last.  A non-zero code raises through `check`, naming `base`
+    (or `what`); raw=True returns the code instead (the tests of the argument checks)."""
+    rc = fn(base if dtype is None else base + "_" + suffix(dtype))(*args, stream_ptr())
+    if raw:
+        return rc
+    check(rc, what or base)

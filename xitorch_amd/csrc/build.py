@@ -10,6 +10,7 @@ import glob
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libxitorch_amd.so")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")     # the public header: every source sees it
 ARCH = "gfx950"
 
 
@@ -24,11 +25,15 @@ def sources():
     return sorted(glob.glob(os.path.join(HERE, "*.hip")))
 
 
+def headers():
+    return glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h"))
+
+
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(HERE, "*.h"))
+    deps = sources() + headers()
     return any(os.path.getmtime(p) > t for p in deps)
 
 
@@ -42,11 +47,10 @@ def build(force=False, verbose=True):
         obj = os.path.join(HERE, "build", os.path.basename(src) + ".o")
         objs.append(obj)
         if (not force and os.path.exists(obj) and os.path.getmtime(obj) > os.path.getmtime(src)
-                and all(os.path.getmtime(obj) > os.path.getmtime(h)
-                        for h in glob.glob(os.path.join(HERE, "*.h")))):
+                and all(os.path.getmtime(obj) > os.path.getmtime(h) for h in headers())):
             continue
         cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-               "-I", HERE, "-c", src, "-o", obj]
+               "-I", HERE, "-I", INCLUDE, "-c", src, "-o", obj]
         if verbose:
             print("[xitorch_amd build]", " ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))

@@ -22,25 +22,7 @@
 #include "xk_common.h"
 #include "xk_lane.h"
 
-extern "C" {
-long xk_dense_mm_workspace_elems(int B, int M, int N, int P, int trans);
-int xk_dense_mm_f64(const double*, const double*, double*, double*, long, int, int, int, int, long, long, long, long,
-                    long, long, int, int, int, void*);
-int xk_dense_mm_f32(const float*, const float*, float*, float*, long, int, int, int, int, long, long, long, long, long,
-                    long, int, int, int, void*);
-int xk_lincomb_f64(const double*, const double*, double*, int, int, int, int, long, long, long, long, long, long, long,
-                   double, double, void*);
-int xk_lincomb_f32(const float*, const float*, float*, int, int, int, int, long, long, long, long, long, long, long,
-                   double, double, void*);
-int xk_ritz_residual_f64(const double*, const double*, const double*, const double*, double*, double*, double*, int,
-                         int, int, int, long, long, long, long, long, long, long, long, long, long, long, long, void*);
-int xk_ritz_residual_f32(const float*, const float*, const float*, const float*, float*, float*, float*, int, int, int,
-                         int, long, long, long, long, long, long, long, long, long, long, long, long, void*);
-int xk_panel_chol_f64(const double*, double*, int*, int, int, long, long, void*);
-int xk_panel_chol_f32(const float*, float*, int*, int, int, long, long, void*);
-int xk_panel_transform_f64(double*, const double*, int, int, int, long, long, void*);
-int xk_panel_transform_f32(float*, const float*, int, int, int, long, long, void*);
-}
+// (the entry points of the other files called below are declared by xitorch_amd.h, which xk_common.h includes)
 
 namespace xk {
 

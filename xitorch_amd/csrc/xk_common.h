@@ -5,13 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the C ABI: every entry point is defined in sight of its prototype (a mismatch is "conflicting types" at the
+// definition), and the status codes XK_OK / XK_ERR_ARG / XK_ERR_UNSUPPORTED live there only
+#include "xitorch_amd.h"
 
 #define XK_WAVE 64
-
-// status codes returned over the C ABI (see include/xitorch_amd.h)
-#define XK_OK 0
-#define XK_ERR_ARG (-1)
-#define XK_ERR_UNSUPPORTED (-2)
 
 #define XK_LAUNCH_CHECK()                       \
   do {                                          \

@@ -667,8 +667,6 @@ static long big_lds_elems(long n, long p, long pb) { (void)p; return 4 * n + 16 
 
 }  // namespace xk
 
-extern "C" int xk_small_eigh_big_batch(int k, int p, int elem_size);
-
 // No process-wide state: the launch shape (workgroups per matrix of the step kernels, their threads) arrives as
 // arguments of the entry point (0 = the measured defaults).  The two measurement switches that give WRONG results by
 // construction — "leave the final kernel after phase n", "skip parts of the step kernel" — exist only in a -DXK_DEBUG

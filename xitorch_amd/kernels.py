@@ -7,7 +7,7 @@ view, xitorch/_utils/tensor.py:21-32, seen as its transpose).
 import os
 import torch
 from xitorch_amd import _capi
-from xitorch_amd._capi import ptr, stream_ptr, check, suffix, fn, require_device
+from xitorch_amd._capi import ptr, stream_ptr, check, suffix, fn, call, require_device
 from ctypes import c_void_p as c_void_p_
 
 __all__ = ["dense_mm"]
@@ -19,6 +19,18 @@ def _panel_strides(X):
         raise _capi.NativeLibraryError("panel must be (B, P, N) with unit stride along N, got shape %s stride %s"
                                        % (tuple(X.shape), X.stride()))
     return X.stride(1), X.stride(0)
+
+
+def _op_strides(A):
+    """(lda, sA) of an operator (M, N) or (B or 1, M, N): row pitch and batch pitch (0 broadcasts the one operator)"""
+    if A.dim() == 2:
+        return A.stride(0), 0
+    return A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+
+
+def _esize(dtype):
+    """element size in bytes the real-panel entry points are told"""
+    return 8 if dtype == torch.float64 else 4
 
 
 _ws_cache = {}
@@ -52,14 +64,10 @@ def dense_mm(A, X, out=None, trans=False, rows_hint=0, stagger=1, wide=True):
     if A.dtype != X.dtype:
         raise _capi.NativeLibraryError("dtype mismatch %s vs %s" % (A.dtype, X.dtype))
     B, P = X.shape[0], X.shape[1]
-    if A.dim() == 2:
-        M, N = A.shape
-        lda, sA = A.stride(0), 0
-    else:
-        if A.shape[0] != B and A.shape[0] != 1:
-            raise _capi.NativeLibraryError("operator batch %d does not match panel batch %d" % (A.shape[0], B))
-        M, N = A.shape[1], A.shape[2]
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+    if A.dim() == 3 and A.shape[0] != B and A.shape[0] != 1:
+        raise _capi.NativeLibraryError("operator batch %d does not match panel batch %d" % (A.shape[0], B))
+    M, N = A.shape[-2], A.shape[-1]
+    lda, sA = _op_strides(A)
     if N > 1 and A.stride(-1) != 1:
         raise _capi.NativeLibraryError("operator matrix must have unit stride along its last dim")
     nin, nout = (M, N) if trans else (N, M)
@@ -82,10 +90,8 @@ def dense_mm(A, X, out=None, trans=False, rows_hint=0, stagger=1, wide=True):
     ws_n = fn("xk_dense_mm_workspace_elems")(B, M, N, P, 1 if trans else 0)
     if ws_n > 0:
         ws = _workspace(ws_n, X.dtype, X.device)
-    rc = fn("xk_dense_mm_" + suffix(X.dtype))(
-        ptr(A), ptr(X), ptr(out), ptr(ws), ws_n, B, M, N, P, lda, sA, ldx, sX, ldy, sY,
-        1 if trans else 0, rows_hint, stagger, stream_ptr())
-    check(rc, "xk_dense_mm")
+    call("xk_dense_mm", X.dtype, ptr(A), ptr(X), ptr(out), ptr(ws), ws_n, B, M, N, P, lda, sA, ldx, sX, ldy, sY,
+         1 if trans else 0, rows_hint, stagger)
     return out
 
 
@@ -111,9 +117,8 @@ def lincomb(V, C, out, k, P, coef_layout="ac", alpha=1.0, beta=0.0):
         sC, sCa, sCc = _cstrides(C, 1, 2)
     else:
         sC, sCa, sCc = _cstrides(C, 2, 1)
-    rc = fn("xk_lincomb_" + suffix(V.dtype))(ptr(V), ptr(C), ptr(out), B, k, N, P, ldv, sV, sC, sCa, sCc,
-                                              ldo, sO, float(alpha), float(beta), stream_ptr())
-    check(rc, "xk_lincomb")
+    call("xk_lincomb", V.dtype, ptr(V), ptr(C), ptr(out), B, k, N, P, ldv, sV, sC, sCa, sCc, ldo, sO, float(alpha),
+         float(beta))
     return out
 
 
@@ -135,10 +140,8 @@ def lincomb_c(V, C, out, k, P, alpha=1.0, beta=0.0, N=None):
         raise _capi.NativeLibraryError("lincomb_c: unit stride along the vector / coefficient axis expected")
     B = V.shape[0]
     N = V.shape[2] if N is None else N
-    rc = fn("xk_lincomb_" + suffix(V.dtype))(ptr(V), ptr(C), ptr(out), B, k, N, P, V.stride(1), V.stride(0),
-                                              C.stride(0), C.stride(1), out.stride(1), out.stride(0), float(alpha),
-                                              float(beta), stream_ptr())
-    check(rc, "xk_lincomb_c")
+    call("xk_lincomb", V.dtype, ptr(V), ptr(C), ptr(out), B, k, N, P, V.stride(1), V.stride(0), C.stride(0),
+         C.stride(1), out.stride(1), out.stride(0), float(alpha), float(beta), what="xk_lincomb_c")
     return out
 
 
@@ -163,9 +166,8 @@ def gmres_gram_c(Q, w, c, scratch, kq, N):
     if scratch.numel() < S * nblk * (kq + 1) * 2:
         raise _capi.NativeLibraryError("gmres_gram_c: scratch holds %d doubles, %d needed"
                                        % (scratch.numel(), S * nblk * (kq + 1) * 2))
-    rc = fn("xk_gmres_gram_" + suffix(Q.dtype))(ptr(Q), ptr(w), ptr(c), ptr(scratch), S, N, kq, Q.stride(1),
-                                                 Q.stride(0), w.stride(0), c.stride(0), nblk, stream_ptr())
-    check(rc, "xk_gmres_gram")
+    call("xk_gmres_gram", Q.dtype, ptr(Q), ptr(w), ptr(c), ptr(scratch), S, N, kq, Q.stride(1), Q.stride(0),
+         w.stride(0), c.stride(0), nblk)
     return c
 
 
@@ -176,10 +178,8 @@ def group_status(rmax, info, flag, status, orth=None):
     re-zeroed."""
     if orth is not None and status.numel() < 5:
         raise _capi.NativeLibraryError("group_status: status needs 5 doubles when orth is given")
-    rc = fn("xk_group_status_" + suffix(rmax.dtype))(ptr(rmax), ptr(info), ptr(flag) if flag is not None else None,
-                                                     ptr(orth) if orth is not None else None,
-                                                     ptr(status), rmax.shape[0], stream_ptr())
-    check(rc, "xk_group_status")
+    call("xk_group_status", rmax.dtype, ptr(rmax), ptr(info), ptr(flag) if flag is not None else None,
+         ptr(orth) if orth is not None else None, ptr(status), rmax.shape[0])
 
 
 def ritz_guard(X, orth, P, N, MX=None):
@@ -195,10 +195,8 @@ def ritz_guard(X, orth, P, N, MX=None):
     if P > 8:
         nws = fn("xk_dense_mm_workspace_elems")(B, P, N, P, 0)
         ws = _workspace(max(nws, 1), X.dtype, X.device)
-    rc = fn("xk_ritz_guard_" + suffix(X.dtype))(ptr(X), ptr(M_), ptr(orth), B, N, P, X.stride(1), X.stride(0),
-                                                 M_.stride(1), M_.stride(0), ptr(gs), (gs.numel() if gs is not None else 0),
-                                                 ptr(ws), nws, stream_ptr())
-    check(rc, "xk_ritz_guard")
+    call("xk_ritz_guard", X.dtype, ptr(X), ptr(M_), ptr(orth), B, N, P, X.stride(1), X.stride(0), M_.stride(1),
+         M_.stride(0), ptr(gs), (gs.numel() if gs is not None else 0), ptr(ws), nws)
 
 
 _gs_cache = {}
@@ -232,11 +230,9 @@ def ritz_residual(V, AV, Y, lam, X, Tn, rmax, k, P):
     if lam.stride(-1) != 1 and P > 1:
         raise _capi.NativeLibraryError("lam must have unit stride along its last dim")
     _check_ritz_shapes(V, AV, Y, lam, X, Tn, k, P)
-    rc = fn("xk_ritz_residual_" + suffix(V.dtype))(
-        ptr(V), ptr(AV), ptr(Y), ptr(lam), ptr(X), ptr(Tn), ptr(rmax), B, k, N, P,
-        V.stride(1), V.stride(0), AV.stride(1), AV.stride(0), Y.stride(0), Y.stride(1), Y.stride(2),
-        lam.stride(0), X.stride(1), X.stride(0), Tn.stride(1), Tn.stride(0), stream_ptr())
-    check(rc, "xk_ritz_residual")
+    call("xk_ritz_residual", V.dtype, ptr(V), ptr(AV), ptr(Y), ptr(lam), ptr(X), ptr(Tn), ptr(rmax), B, k, N, P,
+         V.stride(1), V.stride(0), AV.stride(1), AV.stride(0), Y.stride(0), Y.stride(1), Y.stride(2), lam.stride(0),
+         X.stride(1), X.stride(0), Tn.stride(1), Tn.stride(0))
 
 
 def diag_precond(Tn, d, lam, P, m=None, floor=None):
@@ -253,27 +249,21 @@ def diag_precond(Tn, d, lam, P, m=None, floor=None):
             raise _capi.NativeLibraryError("diag_precond: diagonals must be (B or 1, N), unit stride, dtype of the panel")
     sD = d2.stride(0) if d2.shape[0] == B and B > 1 else (0 if d2.shape[0] == 1 else d2.stride(0))
     sM = 0 if m2 is None or m2.shape[0] == 1 else m2.stride(0)
-    rc = fn("xk_diag_precond_" + suffix(Tn.dtype))(ptr(Tn), ptr(d2), ptr(m2) if m2 is not None else None,
-                                                   ptr(lam), B, N, P, Tn.stride(1), Tn.stride(0), sD, sM,
-                                                   lam.stride(0), float(floor), stream_ptr())
-    check(rc, "xk_diag_precond")
+    call("xk_diag_precond", Tn.dtype, ptr(Tn), ptr(d2), ptr(m2) if m2 is not None else None, ptr(lam), B, N, P,
+         Tn.stride(1), Tn.stride(0), sD, sM, lam.stride(0), float(floor))
 
 
 def panel_chol(G, W, info, P):
     """W[b] = R^-1 with G[b] = R^T R (upper R); info[b] != 0 flags a non-positive pivot.
     G: (B, >=P, >=P) with unit stride along its last dim.  CholeskyQR step of tallqr (tensor.py:16-17)."""
     B = G.shape[0]
-    rc = fn("xk_panel_chol_" + suffix(G.dtype))(ptr(G), ptr(W), ptr(info), B, P, G.stride(1), G.stride(0),
-                                                 stream_ptr())
-    check(rc, "xk_panel_chol")
+    call("xk_panel_chol", G.dtype, ptr(G), ptr(W), ptr(info), B, P, G.stride(1), G.stride(0))
 
 
 def panel_transform(Tp, W, P):
     """In place Tp[b,c,:] <- sum_{a<=c} W[b,a,c] Tp[b,a,:]  (tensor.py:18, Q = V R^-1 for the new panel only)."""
     B, N = Tp.shape[0], Tp.shape[2]
-    rc = fn("xk_panel_transform_" + suffix(Tp.dtype))(ptr(Tp), ptr(W), B, P, N, Tp.stride(1), Tp.stride(0),
-                                                      stream_ptr())
-    check(rc, "xk_panel_transform")
+    call("xk_panel_transform", Tp.dtype, ptr(Tp), ptr(W), B, P, N, Tp.stride(1), Tp.stride(0))
 
 
 # --------------------------------------------------------------------------- Davidson chain (one C call per stage)
@@ -294,13 +284,11 @@ def davidson_ritz(V, AV, Y, lam, X, Tn, rmax, info, flag, status, k, P, cond=Non
             gs = _guard_scratch(B, P, V.dtype, V.device)
             nws = fn("xk_dense_mm_workspace_elems")(B, P, N, P, 0)
             ws = _workspace(max(nws, 1), V.dtype, V.device)
-    rc = fn("xk_davidson_ritz_" + suffix(V.dtype))(
-        ptr(V), ptr(AV), ptr(Y), ptr(lam), ptr(X), ptr(Tn), ptr(rmax), ptr(info), ptr(flag) if flag is not None else None,
-        ptr(cond) if cond is not None else None, ptr(orth) if orth is not None else None, ptr(status), B, k, N, P,
-        V.stride(1), V.stride(0), AV.stride(1), AV.stride(0), Y.stride(0), Y.stride(1),
-        Y.stride(2), lam.stride(0), X.stride(1), X.stride(0), Tn.stride(1), Tn.stride(0),
-        ptr(gs), (gs.numel() if gs is not None else 0), ptr(ws), nws, stream_ptr())
-    check(rc, "xk_davidson_ritz")
+    call("xk_davidson_ritz", V.dtype, ptr(V), ptr(AV), ptr(Y), ptr(lam), ptr(X), ptr(Tn), ptr(rmax), ptr(info),
+         ptr(flag) if flag is not None else None, ptr(cond) if cond is not None else None,
+         ptr(orth) if orth is not None else None, ptr(status), B, k, N, P, V.stride(1), V.stride(0), AV.stride(1),
+         AV.stride(0), Y.stride(0), Y.stride(1), Y.stride(2), lam.stride(0), X.stride(1), X.stride(0), Tn.stride(1),
+         Tn.stride(0), ptr(gs), (gs.numel() if gs is not None else 0), ptr(ws), nws)
 
 
 def davidson_ws(B, cap, N, q, dtype, device):
@@ -317,10 +305,8 @@ def davidson_orth(V, N, k0, q, C, W, info, passes=2, cond=None):
     max(cond, squared pivot ratio of the raw panel)."""
     B = V.shape[0]
     ws, nws = davidson_ws(B, V.shape[1], N, q, V.dtype, V.device)
-    rc = fn("xk_davidson_orth_" + suffix(V.dtype))(ptr(V), B, N, k0, q, V.stride(1), V.stride(0), ptr(C), ptr(W),
-                                                    ptr(info), ptr(cond) if cond is not None else None, ptr(ws), nws,
-                                                    int(passes), stream_ptr())
-    check(rc, "xk_davidson_orth")
+    call("xk_davidson_orth", V.dtype, ptr(V), B, N, k0, q, V.stride(1), V.stride(0), ptr(C), ptr(W), ptr(info),
+         ptr(cond) if cond is not None else None, ptr(ws), nws, int(passes))
 
 
 def davidson_extend_t(V, AV, Tm, Tn, N, k0, q):
@@ -328,10 +314,8 @@ def davidson_extend_t(V, AV, Tm, Tn, N, k0, q):
     the new rows / columns) in one C call.  Tn: scratch of >= B*q*(k0+q) elements."""
     B = V.shape[0]
     ws, nws = davidson_ws(B, V.shape[1], N, q, V.dtype, V.device)
-    rc = fn("xk_davidson_extend_t_" + suffix(V.dtype))(ptr(V), ptr(AV), ptr(Tm), ptr(Tn), B, N, k0, q, V.stride(1),
-                                                        V.stride(0), AV.stride(1), AV.stride(0), Tm.stride(1),
-                                                        Tm.stride(0), ptr(ws), nws, stream_ptr())
-    check(rc, "xk_davidson_extend_t")
+    call("xk_davidson_extend_t", V.dtype, ptr(V), ptr(AV), ptr(Tm), ptr(Tn), B, N, k0, q, V.stride(1), V.stride(0),
+         AV.stride(1), AV.stride(0), Tm.stride(1), Tm.stride(0), ptr(ws), nws)
 
 
 # --------------------------------------------------------------------------- K3 small eigensolver
@@ -346,8 +330,7 @@ def small_eigh_tri_ok(k, p, dtype):
     """does the tridiagonalisation kernel (K3t) serve order k with p wanted pairs?  (LDS-resident: <= 160 KiB)"""
     if k > SMALL_EIGH_MAX_K or p > SMALL_EIGH_MAX_P or p > k:
         return False
-    esize = 8 if dtype == torch.float64 else 4
-    return fn("xk_small_eigh_tri_lds_bytes")(k, p, esize) <= 160 * 1024
+    return fn("xk_small_eigh_tri_lds_bytes")(k, p, _esize(dtype)) <= 160 * 1024
 
 
 SMALL_EIGH_BIG_MAX_K = 1536          # (r06: was 1024; fp64 beyond 614 and fp32 where the band does not fit: one launch per
@@ -366,7 +349,7 @@ def small_eigh_big_ok(k, p, dtype):
     """does the global-memory tridiagonalisation kernel (K3g) serve order k with p wanted pairs?"""
     if k < 8 or k > SMALL_EIGH_BIG_MAX_K or p > SMALL_EIGH_BIG_MAX_P or p > k:
         return False
-    return fn("xk_small_eigh_big_batch")(k, p, 8 if dtype == torch.float64 else 4) > 0
+    return fn("xk_small_eigh_big_batch")(k, p, _esize(dtype)) > 0
 
 
 def small_eigh_big(T, k, p, uppest=False, wg=None, threads=None, algo=None):
@@ -389,10 +372,8 @@ def small_eigh_big(T, k, p, uppest=False, wg=None, threads=None, algo=None):
     if algo < 0:
         # measurement knob: the r05 choice (two-stage from order 192 on where its band fits the LDS, else step launches)
         algo = 2 if k >= 192 and (k <= 614 or T.dtype == torch.float32) else 1
-    rc = fn("xk_small_eigh_big_" + suffix(T.dtype))(ptr(T), ptr(lam), ptr(Y), ptr(ws), nws, ptr(info), B, k, p,
-                                                     1 if uppest else 0, T.stride(1), T.stride(0), wg, threads,
-                                                     algo, stream_ptr())
-    check(rc, "xk_small_eigh_big")
+    call("xk_small_eigh_big", T.dtype, ptr(T), ptr(lam), ptr(Y), ptr(ws), nws, ptr(info), B, k, p, 1 if uppest else 0,
+         T.stride(1), T.stride(0), wg, threads, algo)
     return lam, Y, info
 
 
@@ -410,17 +391,13 @@ def small_eigh(T, k, p, uppest=False, max_sweeps=16, method="jacobi", threads=0,
     Y = torch.empty((B, p, k), dtype=T.dtype, device=T.device)
     aux = torch.empty((B,), dtype=torch.int32, device=T.device)
     if method == "tri":
-        rc = fn("xk_small_eigh_tri_" + suffix(T.dtype))(ptr(T), ptr(lam), ptr(Y), ptr(aux), B, k, p, 1 if uppest else 0,
-                                                         T.stride(1), T.stride(0), int(threads), ptr(profile),
-                                                         stream_ptr())
-        check(rc, "xk_small_eigh_tri")
+        call("xk_small_eigh_tri", T.dtype, ptr(T), ptr(lam), ptr(Y), ptr(aux), B, k, p, 1 if uppest else 0, T.stride(1),
+             T.stride(0), int(threads), ptr(profile))
         return lam, Y, aux
     nws = fn("xk_small_eigh_workspace_elems")(B, k, max_sweeps)
     ws = _workspace(nws, T.dtype, T.device)
-    rc = fn("xk_small_eigh_" + suffix(T.dtype))(ptr(T), ptr(lam), ptr(Y), ptr(ws), nws, ptr(aux), B, k, p,
-                                                 1 if uppest else 0, max_sweeps, T.stride(1), T.stride(0),
-                                                 stream_ptr())
-    check(rc, "xk_small_eigh")
+    call("xk_small_eigh", T.dtype, ptr(T), ptr(lam), ptr(Y), ptr(ws), nws, ptr(aux), B, k, p, 1 if uppest else 0,
+         max_sweeps, T.stride(1), T.stride(0))
     return lam, Y, aux
 
 
@@ -466,9 +443,8 @@ def banded_mm(band, X, out=None, trans=False):
     if out.numel() > 0 and not _rows_disjoint(B, C, N, sY, ldy):
         raise _capi.NativeLibraryError("banded_mm: rows of out overlap (shape %s, strides %s)"
                                        % (tuple(out.shape), out.stride()))
-    rc = fn("xk_banded_mm_" + suffix(X.dtype))(ptr(band), ptr(X), ptr(out), B, N, nd // 2, C, sBand, ldx, sX,
-                                                ldy, sY, 1 if trans else 0, stream_ptr())
-    check(rc, "xk_banded_mm")
+    call("xk_banded_mm", X.dtype, ptr(band), ptr(X), ptr(out), B, N, nd // 2, C, sBand, ldx, sX, ldy, sY,
+         1 if trans else 0)
     return out
 
 
@@ -487,9 +463,8 @@ def banded_grad(U, W, nd, out=None, accumulate=False):
         accumulate = False
     if not out.is_contiguous():
         raise _capi.NativeLibraryError("banded_grad: output must be contiguous")
-    rc = fn("xk_banded_grad_" + suffix(U.dtype))(ptr(U), ptr(W), ptr(out), B, N, nd // 2, C, ldu, sU, ldw, sW,
-                                                  out.stride(0), 1 if accumulate else 0, stream_ptr())
-    check(rc, "xk_banded_grad")
+    call("xk_banded_grad", U.dtype, ptr(U), ptr(W), ptr(out), B, N, nd // 2, C, ldu, sU, ldw, sW, out.stride(0),
+         1 if accumulate else 0)
     return out
 
 
@@ -525,12 +500,10 @@ def csr_mm(pat, values, X, out=None, trans=False):
         raise _capi.NativeLibraryError("output must be (%d, %d, %d), got %s" % (B, C, v.n_out, tuple(out.shape)))
     ldy, sY = _panel_strides(out)
     ws = v.scratch(B * min(C, 8) * v.nseg, X.dtype) if v.nseg else None
-    rc = fn("xk_csr_mm_" + suffix(X.dtype))(ptr(v.ptr), ptr(v.idx), ptr(v.perm), ptr(values), sV, ptr(v.rows),
-                                             v.bin_off, ptr(v.seg_q), ptr(v.seg_off), v.nseg, ptr(ws), ptr(X),
-                                             ptr(out), B, v.n_out, nin, C, ldx if C > 1 else max(ldx, nin), sX,
-                                             ldy if C > 1 else max(ldy, v.n_out), sY,
-                                             *(((1 if trans else 0),) if cplx else ()), stream_ptr())
-    check(rc, "xk_csr_mm")
+    call("xk_csr_mm", X.dtype, ptr(v.ptr), ptr(v.idx), ptr(v.perm), ptr(values), sV, ptr(v.rows), v.bin_off,
+         ptr(v.seg_q), ptr(v.seg_off), v.nseg, ptr(ws), ptr(X), ptr(out), B, v.n_out, nin, C,
+         ldx if C > 1 else max(ldx, nin), sX, ldy if C > 1 else max(ldy, v.n_out), sY,
+         *(((1 if trans else 0),) if cplx else ()))
     return out
 
 
@@ -560,10 +533,8 @@ def csr_sddmm(pat, U, W, out=None):
         out = torch.empty((B, pat.nnz), dtype=U.dtype, device=U.device)
     if out.shape != (B, pat.nnz) or (pat.nnz > 1 and out.stride(-1) != 1):
         raise _capi.NativeLibraryError("csr_sddmm: output must be (%d, %d) with unit stride" % (B, pat.nnz))
-    rc = fn("xk_csr_sddmm_" + suffix(U.dtype))(ptr(pat.row_of), ptr(pat.col), ptr(U), ptr(W), ptr(out), pat.nnz, B,
-                                                M, pat.N, C, ldu if C > 1 else max(ldu, M), sU,
-                                                ldw if C > 1 else max(ldw, pat.N), sW, out.stride(0), stream_ptr())
-    check(rc, "xk_csr_sddmm")
+    call("xk_csr_sddmm", U.dtype, ptr(pat.row_of), ptr(pat.col), ptr(U), ptr(W), ptr(out), pat.nnz, B, M, pat.N, C,
+         ldu if C > 1 else max(ldu, M), sU, ldw if C > 1 else max(ldw, pat.N), sW, out.stride(0))
     return out
 
 
@@ -583,9 +554,8 @@ def dense_outer(U, W, out=None, accumulate=False):
         accumulate = False
     if out.stride(2) != 1 and N > 1:
         raise _capi.NativeLibraryError("dense_outer: output must have unit stride along its last dim")
-    rc = fn("xk_dense_outer_" + suffix(U.dtype))(ptr(U), ptr(W), ptr(out), B, M, N, C, ldu, sU, ldw, sW,
-                                                  out.stride(1), out.stride(0), 1 if accumulate else 0, stream_ptr())
-    check(rc, "xk_dense_outer")
+    call("xk_dense_outer", U.dtype, ptr(U), ptr(W), ptr(out), B, M, N, C, ldu, sU, ldw, sW, out.stride(1),
+         out.stride(0), 1 if accumulate else 0)
     return out
 
 
@@ -619,8 +589,7 @@ def vec_dots(pairs, out=None):
         _vd_scratch[key] = scratch
     if out is None:
         out = torch.empty(np_, dtype=torch.float64, device=a0.device)
-    rc = fn("xk_vec_dots_" + suffix(a0.dtype))(*[ptr(t) for t in flat], np_, L, ptr(scratch), nws, ptr(out), stream_ptr())
-    check(rc, "xk_vec_dots")
+    call("xk_vec_dots", a0.dtype, *[ptr(t) for t in flat], np_, L, ptr(scratch), nws, ptr(out))
     return out
 
 
@@ -630,11 +599,8 @@ def broyden_axpy(out, u0=None, g0=0.0, u1=None, g1=0.0, V=None, coef=None, scale
     require_device(out, "vector")
     L = out.numel()
     ldv = V.stride(-2) if (V is not None and k > 0) else 0
-    rc = fn("xk_broyden_axpy_" + suffix(out.dtype))(ptr(out), ptr(u0), float(g0), ptr(u1), float(g1),
-                                                     ptr(V) if k > 0 else ptr(None), ldv,
-                                                     ptr(coef) if k > 0 else ptr(None), ptr(scale), int(k), float(gamma),
-                                                     L, stream_ptr())
-    check(rc, "xk_broyden_axpy")
+    call("xk_broyden_axpy", out.dtype, ptr(out), ptr(u0), float(g0), ptr(u1), float(g1), ptr(V) if k > 0 else ptr(None),
+         ldv, ptr(coef) if k > 0 else ptr(None), ptr(scale), int(k), float(gamma), L)
     return out
 
 
@@ -647,25 +613,23 @@ def minres_state(S, device):
 def minres_init(y0, v, Pb, state, phi2, S, N, ld, nblk, k):
     """beta = sqrt(<b, y0>) from the xk_kry_dots partials Pb, v = y0 / beta, state slot k & 1, phi2 <- beta^2"""
     require_device(v, "vector")
-    check(fn("xk_minres_init_" + suffix(v.dtype))(ptr(y0), ptr(v), ptr(Pb), ptr(state), ptr(phi2), S, N, ld, nblk,
-                                                  int(k), stream_ptr()), "xk_minres_init")
+    call("xk_minres_init", v.dtype, ptr(y0), ptr(v), ptr(Pb), ptr(state), ptr(phi2), S, N, ld, nblk, int(k))
 
 
 def minres_lanczos(Av, r2, r1, Palpha, state, Pbeta, S, N, ld, nblk, k):
     """r1 <- Av - (alpha / beta) r2 - (beta / beta_old) r1 with alpha from the partials Palpha; Pbeta <- |r1|^2
     partials (None: not wanted).  The caller swaps the roles of r1 and r2 afterwards."""
     require_device(r1, "vector")
-    check(fn("xk_minres_lanczos_" + suffix(r1.dtype))(ptr(Av), ptr(r2), ptr(r1), ptr(Palpha), ptr(state), ptr(Pbeta),
-                                                      S, N, ld, nblk, int(k), stream_ptr()), "xk_minres_lanczos")
+    call("xk_minres_lanczos", r1.dtype, ptr(Av), ptr(r2), ptr(r1), ptr(Palpha), ptr(state), ptr(Pbeta), S, N, ld, nblk,
+         int(k))
 
 
 def minres_update(v, y, w1, w2, x, Palpha, Pbeta, beta_is_dot, state, phi2, S, N, ld, nblk, k):
     """rotation k; w1 <- (v - epsln w1 - delta w2) / gamma; x += phi w1; v <- y / beta_new; state slot (k + 1) & 1;
     phi2 <- phibar^2.  beta_is_dot: Pbeta holds xk_kry_dots partials of <r2, P r2> instead of xk_minres_lanczos' own."""
     require_device(x, "vector")
-    check(fn("xk_minres_update_" + suffix(x.dtype))(ptr(v), ptr(y), ptr(w1), ptr(w2), ptr(x), ptr(Palpha), ptr(Pbeta),
-                                                    1 if beta_is_dot else 0, ptr(state), ptr(phi2), S, N, ld, nblk,
-                                                    int(k), stream_ptr()), "xk_minres_update")
+    call("xk_minres_update", x.dtype, ptr(v), ptr(y), ptr(w1), ptr(w2), ptr(x), ptr(Palpha), ptr(Pbeta),
+         1 if beta_is_dot else 0, ptr(state), ptr(phi2), S, N, ld, nblk, int(k))
 
 
 # --------------------------------------------------------------------------- LSMR step kernels (xk_lsmr.hip)
@@ -677,22 +641,16 @@ def lsmr_state(S, device):
 def lsmr_init(b, uh, Pb, state, run, S, N, ld, nblk, k, raw=False):
     """beta_1 = sqrt(sum Pb) from the |b|^2 partials, uh <- b, start state in slot k & 1, run <- 1 / 0 (b = 0)"""
     require_device(uh, "vector")
-    rc = fn("xk_lsmr_init_" + suffix(uh.dtype))(ptr(b), ptr(uh), ptr(Pb), ptr(state), ptr(run), S, N, ld, nblk, int(k),
-                                                stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_lsmr_init")
+    return call("xk_lsmr_init", uh.dtype, ptr(b), ptr(uh), ptr(Pb), ptr(state), ptr(run), S, N, ld, nblk, int(k),
+                raw=raw)
 
 
 def lsmr_bidiag(Op, y, Pin, Pout, state, half, S, N, ld, nblk, nblk_in, k, raw=False):
     """y <- Op / nu_x - (nu_x / nu_y) y: nu_x from the nblk_in partials Pin, nu_y from the state (half 0, the u half:
     beta; half 1, the v half: alpha); Pout <- the nblk partials of |y|^2"""
     require_device(y, "vector")
-    rc = fn("xk_lsmr_bidiag_" + suffix(y.dtype))(ptr(Op), ptr(y), ptr(Pin), ptr(Pout), ptr(state), int(half), S, N, ld,
-                                                 nblk, nblk_in, int(k), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_lsmr_bidiag")
+    return call("xk_lsmr_bidiag", y.dtype, ptr(Op), ptr(y), ptr(Pin), ptr(Pout), ptr(state), int(half), S, N, ld, nblk,
+                nblk_in, int(k), raw=raw)
 
 
 def lsmr_update(vh, h, hbar, x, Pu, Pv, Pxin, Pxout, state, run, S, N, ld, nblk, nblk_u, k, damp=0.0, atol=1e-6,
@@ -700,12 +658,9 @@ def lsmr_update(vh, h, hbar, x, Pu, Pv, Pxin, Pxout, state, run, S, N, ld, nblk,
     """step k of LSMR on the v side: the rotations, hbar, x and h in one pass, the estimates and the stop code into
     state slot (k + 1) & 1, run <- 1 / 0, Pxout <- partials of |x|^2"""
     require_device(x, "vector")
-    rc = fn("xk_lsmr_update_" + suffix(x.dtype))(ptr(vh), ptr(h), ptr(hbar), ptr(x), ptr(Pu), ptr(Pv), ptr(Pxin),
-                                                 ptr(Pxout), ptr(state), ptr(run), S, N, ld, nblk, nblk_u, int(k),
-                                                 float(damp), float(atol), float(btol), float(conlim), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_lsmr_update")
+    return call("xk_lsmr_update", x.dtype, ptr(vh), ptr(h), ptr(hbar), ptr(x), ptr(Pu), ptr(Pv), ptr(Pxin), ptr(Pxout),
+                ptr(state), ptr(run), S, N, ld, nblk, nblk_u, int(k), float(damp), float(atol), float(btol),
+                float(conlim), raw=raw)
 
 
 # --------------------------------------------------------------------------- Chebyshev filter step (xk_cheb.hip)
@@ -738,11 +693,8 @@ def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
         # (a one-vector panel / a one-member batch may carry any stride there)
         args += [ptr(t), t.stride(1) if (p > 1 or t.stride(1) >= t.shape[2]) else t.shape[2],
                  t.stride(0) if Bt > 1 else 0]
-    rc = fn("xk_cheb_step_" + suffix(AY.dtype))(*args, ptr(coef), Bt, p, int(N), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_cheb_step")
-    return out
+    rc = call("xk_cheb_step", AY.dtype, *args, ptr(coef), Bt, p, int(N), raw=raw)
+    return rc if raw else out
 
 
 # --------------------------------------------------------------------------- complex operators (real embedding)
@@ -855,10 +807,8 @@ def herm_eigh(T, k, p, uppest=False):
     info = torch.empty((B,), dtype=torch.int32, device=T.device)
     nws = fn("xk_herm_eigh_workspace_elems")(B, k, p)
     ws = _workspace(max(nws, 1), rdt, T.device)
-    rc = fn("xk_herm_eigh_" + suffix(T.dtype))(ptr(_real_view(T)), ptr(lam), ptr(_real_view(Y)), ptr(info), ptr(ws),
-                                                nws, B, k, p, 1 if uppest else 0, T.stride(1), T.stride(0),
-                                                stream_ptr())
-    check(rc, "xk_herm_eigh")
+    call("xk_herm_eigh", T.dtype, ptr(_real_view(T)), ptr(lam), ptr(_real_view(Y)), ptr(info), ptr(ws), nws, B, k, p,
+         1 if uppest else 0, T.stride(1), T.stride(0))
     return lam, Y, info
 
 
@@ -879,12 +829,10 @@ def herm_ritz(V, AV, Y, lam, X, Tn, status, k, p, MV=None):
     if status.numel() < B + 1 or status.dtype != torch.float64:
         raise _capi.NativeLibraryError("herm_ritz: status needs B + 1 float64 elements")
     M_ = MV if MV is not None else V
-    rc = fn("xk_herm_ritz_" + suffix(V.dtype))(
-        ptr(_real_view(V)), ptr(_real_view(AV)), ptr(_real_view(MV)) if MV is not None else None, ptr(_real_view(Y)),
-        ptr(lam), ptr(_real_view(X)), ptr(_real_view(Tn)), ptr(status), B, k, N, p, _ld(V), V.stride(0),
-        _ld(AV), AV.stride(0), _ld(M_), M_.stride(0), Y.stride(0), Y.stride(1), Y.stride(2), lam.stride(0),
-        _ld(X), X.stride(0), _ld(Tn), Tn.stride(0), stream_ptr())
-    check(rc, "xk_herm_ritz")
+    call("xk_herm_ritz", V.dtype, ptr(_real_view(V)), ptr(_real_view(AV)),
+         ptr(_real_view(MV)) if MV is not None else None, ptr(_real_view(Y)), ptr(lam), ptr(_real_view(X)),
+         ptr(_real_view(Tn)), ptr(status), B, k, N, p, _ld(V), V.stride(0), _ld(AV), AV.stride(0), _ld(M_),
+         M_.stride(0), Y.stride(0), Y.stride(1), Y.stride(2), lam.stride(0), _ld(X), X.stride(0), _ld(Tn), Tn.stride(0))
 
 
 def herm_cholqr(W, info, MW=None, shift_rel=0.0):
@@ -899,11 +847,9 @@ def herm_cholqr(W, info, MW=None, shift_rel=0.0):
         if t is not None and (t.shape != W.shape or t.stride(2) != 1 or t.dtype != W.dtype):
             raise _capi.NativeLibraryError("herm_cholqr: blocks must be (B, q, N) of one dtype, unit stride along N")
     Rinv = torch.empty((B, q, q), dtype=W.dtype, device=W.device)
-    rc = fn("xk_herm_cholqr_" + suffix(W.dtype))(
-        ptr(_real_view(W)), ptr(_real_view(MW)) if MW is not None else None, ptr(_real_view(Rinv)), ptr(info), B, q, N,
-        _ld(W), W.stride(0), _ld(MW) if MW is not None else 0, MW.stride(0) if MW is not None else 0,
-        float(shift_rel), stream_ptr())
-    check(rc, "xk_herm_cholqr")
+    call("xk_herm_cholqr", W.dtype, ptr(_real_view(W)), ptr(_real_view(MW)) if MW is not None else None,
+         ptr(_real_view(Rinv)), ptr(info), B, q, N, _ld(W), W.stride(0), _ld(MW) if MW is not None else 0,
+         MW.stride(0) if MW is not None else 0, float(shift_rel))
     return Rinv
 
 
@@ -918,8 +864,7 @@ def stream_read(t):
     if pitch % 16:
         raise _capi.NativeLibraryError("stream_read: the row length must be a multiple of 16 bytes")
     nbytes = t.numel() * t.element_size()
-    rc = fn("xk_stream_read")(ptr(t), nbytes, pitch, None, stream_ptr())
-    check(rc, "xk_stream_read")
+    call("xk_stream_read", None, ptr(t), nbytes, pitch, None)
     return nbytes
 
 
@@ -1037,24 +982,17 @@ def dense_symm(A, X, out=None, opts=None):
     require_device(A, "operator matrix")
     require_device(X, "panel")
     B, P, N = X.shape
-    if A.dim() == 2:
-        lda, sA = A.stride(0), 0
-    else:
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+    lda, sA = _op_strides(A)
     if A.shape[-1] != N or A.shape[-2] != N or (N > 1 and A.stride(-1) != 1):
         raise _capi.NativeLibraryError("symmetric operator must be (.., %d, %d) with unit stride" % (N, N))
     ldx, sX = _panel_strides(X)
     if out is None:
         out = torch.empty((B, P, N), dtype=X.dtype, device=X.device)
     ldy, sY = _panel_strides(out)
-    esize = 8 if X.dtype == torch.float64 else 4
-    nws = fn("xk_dense_symm_workspace_elems")(B, N, P, esize)
+    nws = fn("xk_dense_symm_workspace_elems")(B, N, P, _esize(X.dtype))
     ws = _workspace(nws, X.dtype, X.device)
-    rc = fn("xk_dense_symm_" + suffix(X.dtype))(ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, N, P, lda, sA,
-                                                 ldx, sX, ldy, sY,
-                                                 _k1s_opts(torch.cuda.current_stream(), opts, (B, N, X.dtype), lda=lda),
-                                                 stream_ptr())
-    check(rc, "xk_dense_symm")
+    call("xk_dense_symm", X.dtype, ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, ldy, sY,
+         _k1s_opts(torch.cuda.current_stream(), opts, (B, N, X.dtype), lda=lda))
     return out
 
 
@@ -1103,10 +1041,7 @@ def _symm_wide_args(A, X, out):
     if A.dtype != torch.float32 or X.dtype != torch.float32 or out.dtype != torch.float32:
         raise _capi.NativeLibraryError("K1sw serves float32 operators and panels only, got %s / %s / %s"
                                        % (A.dtype, X.dtype, out.dtype))
-    if A.dim() == 2:
-        lda, sA = A.stride(0), 0
-    else:
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+    lda, sA = _op_strides(A)
     if A.shape[-1] != N or A.shape[-2] != N or (N > 1 and A.stride(-1) != 1):
         raise _capi.NativeLibraryError("symmetric operator must be (.., %d, %d) with unit stride" % (N, N))
     ldx, sX = _panel_strides(X)
@@ -1125,9 +1060,8 @@ def dense_symm_wide(A, X, out=None):
         out = torch.empty_like(X)
     B, P, N, lda, sA, ldx, sX, ldy, sY, nws = _symm_wide_args(A, X, out)
     ws = _workspace(nws, X.dtype, X.device)
-    rc = fn("xk_dense_symm_wide_f32")(ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, ldy, sY,
-                                      _k1sw_opts(torch.cuda.current_stream(), B, N), stream_ptr())
-    check(rc, "xk_dense_symm_wide")
+    call("xk_dense_symm_wide", torch.float32, ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, ldy,
+         sY, _k1sw_opts(torch.cuda.current_stream(), B, N))
     return out
 
 
@@ -1148,15 +1082,12 @@ def dense_symm_wide_split(A, X, out, tiles_stream, timed=False):
         if timed:
             e0, e1 = timing_event_pair()
             e0.record(tiles_stream)
-        rc = fn("xk_dense_symm_wide_tiles_f32")(ptr(A), ptr(X), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, wopts,
-                                                stream_ptr())
-        check(rc, "xk_dense_symm_wide_tiles")
+        call("xk_dense_symm_wide_tiles", torch.float32, ptr(A), ptr(X), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, wopts)
         if timed:
             e1.record(tiles_stream)
         done.record(tiles_stream)
     cur.wait_event(done)
-    rc = fn("xk_dense_symm_wide_fold_f32")(ptr(out), ptr(ws), nws, B, N, P, ldy, sY, wopts, stream_ptr())
-    check(rc, "xk_dense_symm_wide_fold")
+    call("xk_dense_symm_wide_fold", torch.float32, ptr(out), ptr(ws), nws, B, N, P, ldy, sY, wopts)
     return e0, e1
 
 
@@ -1205,19 +1136,14 @@ def dense_symm_split(A, X, out, tiles_stream, timed=False):
     B, P, N = X.shape
     if P > 6:
         raise _capi.NativeLibraryError("dense_symm_split serves panels of at most 6 columns")
-    if A.dim() == 2:
-        lda, sA = A.stride(0), 0
-    else:
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+    lda, sA = _op_strides(A)
     ldx, sX = _panel_strides(X)
     ldy, sY = _panel_strides(out)
-    esize = 8 if X.dtype == torch.float64 else 4
-    nws = fn("xk_dense_symm_workspace_elems")(B, N, P, esize)
+    nws = fn("xk_dense_symm_workspace_elems")(B, N, P, _esize(X.dtype))
     cur = torch.cuda.current_stream()
     ws = _workspace(nws, X.dtype, X.device)                 # keyed by the CURRENT (group) stream
     ready, done = sync_events(cur)                          # re-recorded on every launch: no event is created here
     ready.record(cur)
-    sfx = suffix(X.dtype)
     kopts = _k1s_opts(tiles_stream, None, (B, N, X.dtype), pipelined=True, lda=lda)
     e0 = e1 = None
     with torch.cuda.stream(tiles_stream):
@@ -1225,15 +1151,12 @@ def dense_symm_split(A, X, out, tiles_stream, timed=False):
         if timed:
             e0, e1 = timing_event_pair()
             e0.record(tiles_stream)
-        rc = fn("xk_dense_symm_tiles_" + sfx)(ptr(A), ptr(X), ptr(ws), nws, B, N, P, lda, sA, ldx, sX,
-                                              kopts, stream_ptr())
-        check(rc, "xk_dense_symm_tiles")
+        call("xk_dense_symm_tiles", X.dtype, ptr(A), ptr(X), ptr(ws), nws, B, N, P, lda, sA, ldx, sX, kopts)
         if timed:
             e1.record(tiles_stream)
         done.record(tiles_stream)
     cur.wait_event(done)
-    rc = fn("xk_dense_symm_fold_" + sfx)(ptr(out), ptr(ws), nws, B, N, P, ldy, sY, kopts, stream_ptr())
-    check(rc, "xk_dense_symm_fold")
+    call("xk_dense_symm_fold", X.dtype, ptr(out), ptr(ws), nws, B, N, P, ldy, sY, kopts)
     return e0, e1
 
 
@@ -1254,24 +1177,17 @@ def dense_rows_wide(A, X, out=None):
     require_device(A, "operator matrix")
     require_device(X, "panel")
     B, P, N = X.shape
-    if A.dim() == 2:
-        M = A.shape[0]
-        lda, sA = A.stride(0), 0
-    else:
-        M = A.shape[1]
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
+    M = A.shape[-2]
+    lda, sA = _op_strides(A)
     if A.shape[-1] != N:
         raise _capi.NativeLibraryError("panel length %d != operator columns %d" % (N, A.shape[-1]))
     ldx, sX = _panel_strides(X)
     if out is None:
         out = torch.empty((B, P, M), dtype=X.dtype, device=X.device)
     ldy, sY = _panel_strides(out)
-    esize = 8 if X.dtype == torch.float64 else 4
-    nws = fn("xk_dense_rows_wide_workspace_elems")(B, M, N, P, esize)
+    nws = fn("xk_dense_rows_wide_workspace_elems")(B, M, N, P, _esize(X.dtype))
     ws = _workspace(nws, X.dtype, X.device) if nws > 0 else None
-    rc = fn("xk_dense_rows_wide_" + suffix(X.dtype))(ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, M, N, P, lda, sA,
-                                                      ldx, sX, ldy, sY, stream_ptr())
-    check(rc, "xk_dense_rows_wide")
+    call("xk_dense_rows_wide", X.dtype, ptr(A), ptr(X), ptr(out), ptr(ws), nws, B, M, N, P, lda, sA, ldx, sX, ldy, sY)
     return out
 
 
@@ -1287,15 +1203,11 @@ def dense_wide(A, X, out=None):
     require_device(A, "operator matrix")
     require_device(X, "panel")
     B, P, M = X.shape
-    if A.dim() == 2:
-        lda, sA = A.stride(0), 0
-        N = A.shape[1]
-    else:
-        lda, sA = A.stride(1), (A.stride(0) if A.shape[0] != 1 else 0)
-        N = A.shape[2]
+    N = A.shape[-1]
+    lda, sA = _op_strides(A)
     if A.shape[-2] != M:
         raise _capi.NativeLibraryError("panel length %d != operator rows %d" % (M, A.shape[-2]))
-    esize = 8 if X.dtype == torch.float64 else 4
+    esize = _esize(X.dtype)
     PP = fn("xk_dense_wide_padded_width")(P, esize)
     Xrm = torch.zeros((B, M, PP), dtype=X.dtype, device=X.device)      # row-major, zero-padded to whole tiles
     Xrm[:, :, :P].copy_(X.transpose(1, 2))
@@ -1304,9 +1216,8 @@ def dense_wide(A, X, out=None):
     ldy, sY = _panel_strides(out)
     nws = fn("xk_dense_wide_workspace_elems")(B, M, N, P, esize)
     ws = _workspace(nws, X.dtype, X.device)
-    rc = fn("xk_dense_wide_" + suffix(X.dtype))(ptr(A), ptr(Xrm), ptr(out), ptr(ws), nws, B, M, N, P, lda, sA,
-                                                 Xrm.stride(1), Xrm.stride(0), ldy, sY, stream_ptr())
-    check(rc, "xk_dense_wide")
+    call("xk_dense_wide", X.dtype, ptr(A), ptr(Xrm), ptr(out), ptr(ws), nws, B, M, N, P, lda, sA, Xrm.stride(1),
+         Xrm.stride(0), ldy, sY)
     return out
 
 
@@ -1353,15 +1264,12 @@ def gkl_sweep(Q, j, w, dst, coef, scale, part, N, raw=False):
     if part.dtype != torch.float64 or not part.is_contiguous():
         raise _capi.NativeLibraryError("gkl_sweep: part must be a contiguous float64 tensor")
     one = Bt == 1
-    rc = fn("xk_gkl_sweep_" + suffix(w.dtype))(
-        ptr(Q if j > 0 else None), Q.stride(1) if j > 0 else 0, 0 if (one or j == 0) else Q.stride(0),
-        ptr(w), 0 if one else w.stride(0), ptr(dst), 0 if one else dst.stride(0),
-        ptr(coef), 0 if (coef is None or one) else coef.stride(0), ptr(scale), ptr(part), part.numel(),
-        Bt, int(j), int(N), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_gkl_sweep")
-    return dst
+    rc = call("xk_gkl_sweep", w.dtype,
+              ptr(Q if j > 0 else None), Q.stride(1) if j > 0 else 0, 0 if (one or j == 0) else Q.stride(0),
+              ptr(w), 0 if one else w.stride(0), ptr(dst), 0 if one else dst.stride(0),
+              ptr(coef), 0 if (coef is None or one) else coef.stride(0), ptr(scale), ptr(part), part.numel(),
+              Bt, int(j), int(N), raw=raw)
+    return rc if raw else dst
 
 
 def gkl_finish(part, Bt, nval, nchunk, coef, nrm, rnrm, dst=None, smax=None, u=0.0, brk=None, code=0, raw=False):
@@ -1374,13 +1282,9 @@ def gkl_finish(part, Bt, nval, nchunk, coef, nrm, rnrm, dst=None, smax=None, u=0
         if dst.dtype != torch.float64 or dst.dim() != 1 or dst.shape[0] != Bt:
             raise _capi.NativeLibraryError("gkl_finish: dst must be a (Bt,) float64 view")
         sdst = dst.stride(0) if Bt > 1 else 0
-    rc = fn("xk_gkl_finish")(ptr(part), Bt, int(nval), int(nchunk), ptr(coef),
-                             0 if (coef is None or Bt == 1) else coef.stride(0), ptr(nrm), ptr(rnrm), ptr(dst), sdst,
-                             ptr(smax),
-                             float(u), ptr(brk), int(code), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_gkl_finish")
+    return call("xk_gkl_finish", None, ptr(part), Bt, int(nval), int(nchunk), ptr(coef),
+                0 if (coef is None or Bt == 1) else coef.stride(0), ptr(nrm), ptr(rnrm), ptr(dst), sdst, ptr(smax),
+                float(u), ptr(brk), int(code), raw=raw)
 
 
 def gkl_bsvd(Bm, beta=None, smax=None, brk=None, k=0, keep=0, descending=True, tol=0.0, Bnext=None, out=None,
@@ -1397,12 +1301,9 @@ def gkl_bsvd(Bm, beta=None, smax=None, brk=None, k=0, keep=0, descending=True, t
         mk = lambda *s: torch.empty(s, dtype=torch.float64, device=Bm.device)
         out = (mk(Bt, n), mk(Bt, n, n), mk(Bt, n, n), mk(Bt, n), torch.zeros((Bt, 4), dtype=torch.int32, device=Bm.device))
     sigma, P, Q, res, status = out
-    rc = fn("xk_gkl_bsvd")(ptr(Bm), ptr(beta), ptr(smax), ptr(brk), Bt, n, int(k), int(keep), 1 if descending else 0,
-                           float(tol), ptr(sigma), ptr(P), ptr(Q), ptr(res), ptr(status), ptr(Bnext), stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_gkl_bsvd")
-    return out
+    rc = call("xk_gkl_bsvd", None, ptr(Bm), ptr(beta), ptr(smax), ptr(brk), Bt, n, int(k), int(keep),
+              1 if descending else 0, float(tol), ptr(sigma), ptr(P), ptr(Q), ptr(res), ptr(status), ptr(Bnext), raw=raw)
+    return rc if raw else out
 
 
 # --------------------------------------------------------------------------- FSAI preconditioner build
@@ -1458,11 +1359,6 @@ def fsai_build(a_ptr, a_idx, a_val, g_ptr, g_idx, N, out=None, nfail=None, check
         raise _capi.NativeLibraryError("fsai_build: the output must be a contiguous (%d, %d) tensor" % (B, g_nnz))
     if nfail is None:
         nfail = torch.zeros((B,), dtype=torch.int32, device=a_val.device)
-    rc = fn("xk_fsai_build_" + suffix(a_val.dtype))(ptr(a_ptr), ptr(a_idx), ptr(a_val),
-                                                    a_val.stride(0) if B > 1 else 0, a_nnz, ptr(g_ptr), ptr(g_idx),
-                                                    ptr(out), out.stride(0) if B > 1 else 0, g_nnz, ptr(nfail), int(N),
-                                                    B, stream_ptr())
-    if raw:
-        return rc
-    check(rc, "xk_fsai_build")
-    return out, nfail
+    rc = call("xk_fsai_build", a_val.dtype, ptr(a_ptr), ptr(a_idx), ptr(a_val), a_val.stride(0) if B > 1 else 0, a_nnz,
+              ptr(g_ptr), ptr(g_idx), ptr(out), out.stride(0) if B > 1 else 0, g_nnz, ptr(nfail), int(N), B, raw=raw)
+    return rc if raw else (out, nfail)

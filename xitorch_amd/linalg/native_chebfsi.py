@@ -22,7 +22,7 @@ converged columns.
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, check, suffix, stream_ptr
+from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
 from xitorch_amd._util import ConvergenceWarning
 from xitorch_amd.linalg._panel import PanelOperator, pad_len
 from xitorch_amd.linalg import host_eig
@@ -183,13 +183,12 @@ def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
     ld = pad_len(N)
     vn = {torch.float64: 2, torch.float32: 4, torch.complex128: 1, torch.complex64: 2}[dtype]
     nblk = max(1, min(fn("xk_kry_max_partials")(), (N + 256 * vn * 4 - 1) // (256 * vn * 4)))
-    dots_fn = fn("xk_kry_dots_" + suffix(dtype))
     extra = (0,) if cplx else ()
 
     def dot(x, y):
         P = torch.zeros((Bt, 64, 2) if cplx else (Bt, 64), dtype=rdt, device=device)
-        check(dots_fn(ptr(x), ptr(y), ptr(None), ptr(None), ptr(None), ptr(None), ptr(P), ptr(None), Bt, N, ld, nblk,
-                      *extra, stream_ptr()), "xk_kry_dots")
+        call("xk_kry_dots", dtype, ptr(x), ptr(y), ptr(None), ptr(None), ptr(None), ptr(None), ptr(P), ptr(None), Bt, N,
+             ld, nblk, *extra)
         P = P[:, :nblk, 0] if cplx else P[:, :nblk]
         return P.to(torch.float64).sum(dim=1)
 

@@ -17,7 +17,7 @@ Q11); here the shift is simply a per-system scalar.
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, stream_ptr, check, suffix
+from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
 from xitorch_amd._util import bcast_shape, pad_shapes, ConvergenceWarning
 from xitorch_amd.linalg._panel import PanelOperator, pad_len, to_panel, from_panel
 from xitorch_amd.dist import allreduce_max_, all_ranks_agree_true
@@ -147,9 +147,8 @@ class _Problem:
         if self._scratchP is None:
             self._scratchP = torch.zeros((self.S, 64, 2 if self.cplx else 1), dtype=self.rdtype, device=self.device)
         extra = (0,) if self.cplx else ()
-        check(fn("xk_kry_dots_" + suffix(self.dtype))(ptr(out), ptr(out), ptr(None), ptr(None), ptr(Z), ptr(self.E),
-                                                      ptr(self._scratchP), ptr(None), self.S, self.N, self.ld,
-                                                      self.nblk(), *extra, stream_ptr()), "xk_kry_dots")
+        call("xk_kry_dots", self.dtype, ptr(out), ptr(out), ptr(None), ptr(None), ptr(Z), ptr(self.E),
+             ptr(self._scratchP), ptr(None), self.S, self.N, self.ld, self.nblk(), *extra)
 
     def _apply1(self, X, out, trans=False, defer=False):
         """out = A X - E * (M X)  (solve.py:590-604).  defer=True leaves the shift to the caller's next
@@ -217,8 +216,6 @@ class _Kry:
 
     def __init__(self, prob):
         self.S, self.N, self.ld = prob.S, prob.N, prob.ld
-        self.sfx = suffix(prob.dtype)                      # f64 / f32 / c128 / c64: the vector kernels
-        self.rsfx = suffix(prob.rdtype)                    # the (real) status kernel
         self.cplx = prob.cplx
         self.nblk = prob.nblk()
         self.dtype, self.rdtype, self.device = prob.dtype, prob.rdtype, prob.device
@@ -242,29 +239,26 @@ class _Kry:
         t[:, 0] = val
         return t
 
-    def _c(self, name, *args):
-        check(fn("xk_%s_%s" % (name, self.sfx))(*args, stream_ptr()), "xk_" + name)
-
     def dots(self, x1, y1, P1, x2=None, y2=None, P2=None, shift=None, conj1=False):
         """partials of <x1,y1> (and <x2,y2>), <x,y> = sum conj(x) y; shift = Z: first y1 -= E * Z in the same pass
         (the `- M X E` term of the operator, solve.py:590-595, folded into the reduction that follows every apply);
         conj1 (complex only): P1 <- <y1,x1> instead."""
         extra = ((1 if conj1 else 0),) if self.cplx else ()
-        self._c("kry_dots", ptr(x1), ptr(y1), ptr(x2), ptr(y2), ptr(shift), ptr(self.E if shift is not None else None),
-                ptr(P1), ptr(P2), self.S, self.N, self.ld, self.nblk, *extra)
+        call("xk_kry_dots", self.dtype, ptr(x1), ptr(y1), ptr(x2), ptr(y2), ptr(shift),
+             ptr(self.E if shift is not None else None), ptr(P1), ptr(P2), self.S, self.N, self.ld, self.nblk, *extra)
 
     def bicg_p(self, r, p, v, Prho, rho_old, alpha, omega, rho_store, eps, first):
-        self._c("bicg_p", ptr(r), ptr(p), ptr(v), ptr(Prho), ptr(rho_old), ptr(alpha), ptr(omega),
-                ptr(rho_store), self.S, self.N, self.ld, self.nblk, float(eps), 1 if first else 0)
+        call("xk_bicg_p", self.dtype, ptr(r), ptr(p), ptr(v), ptr(Prho), ptr(rho_old), ptr(alpha), ptr(omega),
+             ptr(rho_store), self.S, self.N, self.ld, self.nblk, float(eps), 1 if first else 0)
 
     def bicg_s(self, r, v, s, rho, Pr0v, alpha, eps):
-        self._c("bicg_s", ptr(r), ptr(v), ptr(s), ptr(rho), ptr(Pr0v), ptr(alpha), self.S, self.N, self.ld,
-                self.nblk, float(eps))
+        call("xk_bicg_s", self.dtype, ptr(r), ptr(v), ptr(s), ptr(rho), ptr(Pr0v), ptr(alpha), self.S, self.N, self.ld,
+             self.nblk, float(eps))
 
     def bicg_final(self, x, xout, yd, zd, s, t, r, r0, alpha, Pts, Ptt, omega, Prr, Prho, eps, skip_r):
-        self._c("bicg_final", ptr(x), ptr(xout), ptr(yd), ptr(zd), ptr(s), ptr(t), ptr(r), ptr(r0), ptr(alpha),
-                ptr(Pts), ptr(Ptt), ptr(omega), ptr(Prr), ptr(Prho), self.S, self.N, self.ld, self.nblk,
-                float(eps), 1 if skip_r else 0)
+        call("xk_bicg_final", self.dtype, ptr(x), ptr(xout), ptr(yd), ptr(zd), ptr(s), ptr(t), ptr(r), ptr(r0),
+             ptr(alpha), ptr(Pts), ptr(Ptt), ptr(omega), ptr(Prr), ptr(Prho), self.S, self.N, self.ld, self.nblk,
+             float(eps), 1 if skip_r else 0)
 
     def resid(self, b, y, r, r0, Prr, Prho, init=False):
         """r = b - y with partials |r|^2 -> Prr (real) and <r0, r> -> Prho; init=True: only the partials of the
@@ -273,26 +267,26 @@ class _Kry:
             if getattr(self, "_zero", None) is None or self._zero.shape != b.shape:
                 self._zero = torch.zeros_like(b)
             self._scr = torch.empty_like(b)
-            self._c("kry_resid", ptr(b), ptr(self._zero), ptr(self._scr), ptr(r0), ptr(Prr), ptr(Prho), self.S,
-                    self.N, self.ld, self.nblk)
+            call("xk_kry_resid", self.dtype, ptr(b), ptr(self._zero), ptr(self._scr), ptr(r0), ptr(Prr), ptr(Prho),
+                 self.S, self.N, self.ld, self.nblk)
             self._scr = None
             return
-        self._c("kry_resid", ptr(b), ptr(y), ptr(r), ptr(r0), ptr(Prr), ptr(Prho), self.S, self.N, self.ld,
-                self.nblk)
+        call("xk_kry_resid", self.dtype, ptr(b), ptr(y), ptr(r), ptr(r0), ptr(Prr), ptr(Prho), self.S, self.N, self.ld,
+             self.nblk)
 
     def cg_update(self, x, xout, p, Ap, r, Prz, PpAp, Prr, eps, skip_r):
-        self._c("cg_update", ptr(x), ptr(xout), ptr(p), ptr(Ap), ptr(r), ptr(Prz), ptr(PpAp), ptr(Prr),
-                self.S, self.N, self.ld, self.nblk, float(eps), 1 if skip_r else 0)
+        call("xk_cg_update", self.dtype, ptr(x), ptr(xout), ptr(p), ptr(Ap), ptr(r), ptr(Prz), ptr(PpAp), ptr(Prr),
+             self.S, self.N, self.ld, self.nblk, float(eps), 1 if skip_r else 0)
 
     def cg_p(self, z, p, Prz_new, Prz_old, eps):
-        self._c("cg_p", ptr(z), ptr(p), ptr(Prz_new), ptr(Prz_old), self.S, self.N, self.ld, self.nblk,
-                float(eps))
+        call("xk_cg_p", self.dtype, ptr(z), ptr(p), ptr(Prz_new), ptr(Prz_old), self.S, self.N, self.ld, self.nblk,
+             float(eps))
 
     def check_status(self, Prr, stop, process_group=None, nblk=None):
         """-> (max residual norm over all systems, number of unconverged systems): the one host sync.
         nblk: partials per system held by Prr (default: the block count of the vector kernels)."""
-        check(fn("xk_kry_status_" + self.rsfx)(ptr(Prr), ptr(stop), ptr(self.rnorm), ptr(self.status), self.S,
-                                               self.nblk if nblk is None else nblk, stream_ptr()), "xk_kry_status")
+        call("xk_kry_status", self.rdtype, ptr(Prr), ptr(stop), ptr(self.rnorm), ptr(self.status), self.S,
+             self.nblk if nblk is None else nblk)
         # MAX over the ranks of both entries: max residual, and "someone is unconverged" (count > 0)
         allreduce_max_(self.status, process_group)
         mx, nbad = self.status.tolist()
@@ -630,7 +624,6 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     kr = _Kry(prob)
     S, N, ld = prob.S, prob.N, prob.ld
     dtype, dev = prob.dtype, prob.device
-    sfx = suffix(dtype)
     stop = _stop_vector(prob, rtol, atol)
     every = max(1, int(resid_calc_every))
     msteps = min(nr, max_niter) - 1           # Arnoldi steps whose column enters an iterate (solve.py:389,403)
@@ -680,13 +673,11 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         rtrue = prob.new()
 
         def status_of(Prr, nblk, slot):
-            check(fn("xk_kry_status_" + kr.rsfx)(ptr(Prr), ptr(stop), ptr(kr.rnorm), ptr(status4[2 * slot:]), S, nblk,
-                                                 stream_ptr()), "xk_kry_status")
+            call("xk_kry_status", kr.rdtype, ptr(Prr), ptr(stop), ptr(kr.rnorm), ptr(status4[2 * slot:]), S, nblk)
 
         def true_residual(kd):
             """x = Q y with R y = g (the reference's lstsq solution, :403-410), r = B - A x (:414): partials -> Ptrue"""
-            check(fn("xk_gmres_solve_" + sfx)(ptr(st.R), ptr(st.g), ptr(ycoef), ycoef.stride(0), S, kd, st.cap,
-                                              stream_ptr()), "xk_gmres_solve")
+            call("xk_gmres_solve", dtype, ptr(st.R), ptr(st.g), ptr(ycoef), ycoef.stride(0), S, kd, st.cap)
             x = xbufs[cur_i]
             if prob.cplx:
                 K.lincomb_c(Q, ycoef, x, kd, 1, alpha=1.0, beta=0.0, N=N)
@@ -734,11 +725,10 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                 c1 = K.dense_mm(Q[:, :j + 1, :N], wrow[:, :, :N])                  # (S, 1, j+1): <q_i, w>
                 K.lincomb(Q, c1, wrow, j + 1, 1, coef_layout="ca", alpha=-1.0, beta=1.0)
                 c2n = K.dense_mm(Q[:, :j + 2, :N], wrow[:, :, :N])                 # second pass; last entry |w1|^2
-            check(fn("xk_gmres_step_" + sfx)(ptr(c1), c1.stride(0), ptr(c2n), c2n.stride(0), j, st.cap, ptr(st.R),
-                                             ptr(st.cs), ptr(st.sn), ptr(st.g), ptr(inv_hn), ptr(Pest), S,
-                                             stream_ptr()), "xk_gmres_step")
-            check(fn("xk_gmres_finish_" + sfx)(ptr(Q), ptr(c2n), c2n.stride(0), ptr(inv_hn), S, N, j, Q.stride(1),
-                                               Q.stride(0), stream_ptr()), "xk_gmres_finish")
+            call("xk_gmres_step", dtype, ptr(c1), c1.stride(0), ptr(c2n), c2n.stride(0), j, st.cap, ptr(st.R),
+                 ptr(st.cs), ptr(st.sn), ptr(st.g), ptr(inv_hn), ptr(Pest), S)
+            call("xk_gmres_finish", dtype, ptr(Q), ptr(c2n), c2n.stride(0), ptr(inv_hn), S, N, j, Q.stride(1),
+                 Q.stride(0))
             status_of(Pest, 1, 0)
             cycle_end = restart is not None and j + 1 == mcyc
             checked = (k + 1) % every == 0 or k == msteps - 1 or cycle_end

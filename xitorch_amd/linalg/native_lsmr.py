@@ -21,7 +21,7 @@ Not built: preconditioning, warm start, batch sharding, a dense `exact` method, 
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, stream_ptr, check, suffix
+from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
 from xitorch_amd._util import ConvergenceWarning, bcast_shape
 from xitorch_amd.linalg._panel import pad_len, to_panel, from_panel
 from xitorch_amd.linalg.native_gkl import _RectOperator
@@ -80,10 +80,8 @@ class _Side:
 
     def resid(self, b, y, r, Prr):
         """r = b - y (y None: r is scratch, only the partials of |b|^2 are wanted), Prr <- block partials of |r|^2"""
-        check(fn("xk_kry_resid_" + suffix(self.dtype))(ptr(b), ptr(self.zero if y is None else y),
-                                                       ptr(self.scr if r is None else r), ptr(None), ptr(Prr),
-                                                       ptr(None), self.S, self.N, self.ld, self.nblk, stream_ptr()),
-              "xk_kry_resid")
+        call("xk_kry_resid", self.dtype, ptr(b), ptr(self.zero if y is None else y), ptr(self.scr if r is None else r),
+             ptr(None), ptr(Prr), ptr(None), self.S, self.N, self.ld, self.nblk)
 
     def norm(self, P):
         return P[:, :self.nblk].double().sum(-1).sqrt()
@@ -141,8 +139,7 @@ def lsmr(A, B, damp=0.0, stack=None, **options):
     k = [0]
 
     def running():
-        check(fn("xk_kry_status_" + suffix(rdtype))(ptr(runp), ptr(half), ptr(rnorm), ptr(status), S, 1, stream_ptr()),
-              "xk_kry_status")
+        call("xk_kry_status", rdtype, ptr(runp), ptr(half), ptr(rnorm), ptr(status), S, 1)
         tr["host_reads"] += 1
         return int(status.tolist()[1])                                # the one word the host reads
 
