@@ -66,7 +66,7 @@ def pass_rates(dev, m, n, Bt, nc):
     for dtype in (torch.float64, torch.float32):
         s = torch.empty((), dtype=dtype).element_size()
         S = Bt * nc
-        U, V = _Side(m, Bt, nc, dtype, dtype, dev), _Side(n, Bt, nc, dtype, dtype, dev)
+        U, V = _Side(m, Bt, nc, dtype, dev), _Side(n, Bt, nc, dtype, dev)
         rnd = lambda side: torch.randn(side.shape, dtype=dtype, device=dev)
         opu, uh, opv, vh, h, hbar, x = rnd(U), rnd(U), rnd(V), rnd(V), rnd(V), rnd(V), rnd(V)
         Pu, Pv, Px0, Px1, run = (V.partial() for _ in range(5))

@@ -329,7 +329,7 @@ IDS = ["f64", "f32", "c128", "c64"]
 
 
 def default_nblk(dtype, N):
-    """the driver's sizing rule (native_krylov._Problem.nblk)"""
+    """the driver's sizing rule (linalg._panel.kry_blocks), restated"""
     vn = kref.VEC_ELEMS[dtype]
     return max(1, min(64, (N + 256 * vn * 4 - 1) // (256 * vn * 4)))
 

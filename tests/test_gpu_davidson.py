@@ -147,7 +147,7 @@ def test_device_operators_never_reach_the_host_drivers(dev, monkeypatch):
     """Device dispatch (r06): an operator in HOST memory is served by xitorch_amd/linalg/host_*.py, an operator on the HIP
     device by the HIP kernels and by nothing else — the host drivers' call counters do not move during device calls, a
     host driver refuses a device operator, and a device call FAILS (no silent detour) when the native library is gone."""
-    from xitorch_amd.linalg import host_eig, host_krylov, native_krylov as nk
+    from xitorch_amd.linalg import host_eig, host_krylov, native_krylov as nk, _panel
     from xitorch_amd.optimize import native_root as nr
     from xitorch_amd import _capi
     g = torch.Generator().manual_seed(3)
@@ -178,7 +178,7 @@ def test_device_operators_never_reach_the_host_drivers(dev, monkeypatch):
         raise _capi.NativeLibraryError("libxitorch_amd.so not found (simulated)")
     monkeypatch.setattr(_capi, "fn", gone)
     monkeypatch.setattr(K, "fn", gone)
-    monkeypatch.setattr(nk, "fn", gone)
+    monkeypatch.setattr(_panel, "fn", gone)          # (the drivers' one direct use of fn: kry_blocks)
     with pytest.raises(_capi.NativeLibraryError):
         nk.cg(Ad, Bm.to(dev), rtol=1e-9)
     with pytest.raises(_capi.NativeLibraryError):

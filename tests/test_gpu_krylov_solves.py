@@ -3,7 +3,7 @@
 * float32 / complex64 (Hermitian and not, with and without E / M, a resid_calc_every refresh) against a
   float64 / complex128 dense solve, and against the oracle run in the SAME dtype: same convergence flag, iteration
   count within a small slack.
-* all four dtypes on dense operators of order 5000, where _Problem.nblk() picks 2..63 blocks per system, and on an
+* all four dtypes on dense operators of order 5000, where kry_blocks() picks 2..63 blocks per system, and on an
   implicit tridiagonal operator of order 300 000, beyond the 64-block cap, against a known float64 / complex128
   solution.
 

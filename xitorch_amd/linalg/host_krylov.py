@@ -20,7 +20,7 @@ from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape, ConvergenceWarning
 from xitorch_amd.dist import allreduce_max_, all_ranks_agree_true
 
-__all__ = ["cg", "bicgstab", "gmres", "minres", "scipy_gmres"]
+__all__ = ["cg", "bicgstab", "gmres", "minres", "scipy_gmres", "get_batchdims", "zero_solution"]
 
 calls = {"cg": 0, "bicgstab": 0, "gmres": 0, "minres": 0, "scipy_gmres": 0}        # how often each host driver ran (tests assert 0 on the GPU path)
 
@@ -109,7 +109,8 @@ class _HostProblem:
         return bool(torch.all(torch.logical_or(-mostneg <= offset, neg)).item())
 
 
-def _batchdims(A, B, E, M):
+def get_batchdims(A, B, E, M):
+    """Broadcast batch shape of the solution (reference: _get_batchdims, solve.py:540-549)."""
     shapes = [A.shape[:-2], B.shape[:-2]]
     if E is not None:
         shapes.append(E.shape[:-1])
@@ -118,13 +119,30 @@ def _batchdims(A, B, E, M):
     return bcast_shape(*shapes)
 
 
-def _zero_solution(A, B, bdims):
+def zero_solution(A, B, bdims):
     return torch.zeros((*bdims, A.shape[-1], B.shape[-1]), dtype=A.dtype, device=A.device)
 
 
-def _stop_of(prob, rtol, atol):
+def _setup(A, B, E, M, posdef, need_hermit, max_niter, rtol, atol, process_group, niter_factor=1.5):
+    """What the four methods start with -> (X, prob, stop, max_niter): X is the zero solution of a zero right-hand side
+    (every rank takes that shortcut or none does: the loops contain collectives), else None."""
+    if max_niter is None:
+        max_niter = int(niter_factor * A.shape[-1])
+    bdims = get_batchdims(A, B, E, M)
+    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
+        return zero_solution(A, B, bdims), None, None, max_niter
+    prob = _HostProblem(A, B, E, M, bdims, posdef, need_hermit)
     bn = _colnorm(prob.rhs)
-    return torch.max(rtol * bn, atol * torch.ones_like(bn))
+    return None, prob, torch.max(rtol * bn, atol * torch.ones_like(bn)), max_niter
+
+
+def _finish(X, prob, trace, converged, best, niter, said_niter, resid="resid", **more):
+    if trace is not None:
+        trace.update(niter=niter, napply=prob.napply, converged=converged, best_resid=best, **more)
+    if not converged:
+        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
+                                         "Max norm of %s: %.3e" % (said_niter, resid, best)))
+    return X
 
 
 def _status(rnorm, stop, process_group):
@@ -149,14 +167,10 @@ def cg(A, B, E=None, M=None, posdef=None, precond=None, max_niter=None, rtol=1e-
     """Preconditioned conjugate gradients in host memory (reference: cg, solve.py:69-190); options as
     `native_krylov.cg`."""
     calls["cg"] += 1
-    if max_niter is None:
-        max_niter = int(1.5 * A.shape[-1])
-    bdims = _batchdims(A, B, E, M)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zero_solution(A, B, bdims)
-    prob = _HostProblem(A, B, E, M, bdims, posdef, need_hermit=True)
+    X0, prob, stop, max_niter = _setup(A, B, E, M, posdef, True, max_niter, rtol, atol, process_group)
+    if X0 is not None:
+        return X0
     pre = _precond(precond)
-    stop = _stop_of(prob, rtol, atol)
     x = torch.zeros(prob.shape, dtype=prob.dtype)
     r = prob.rhs                                                    # x0 = 0
     z = pre(r) if pre is not None else r
@@ -186,12 +200,7 @@ def cg(A, B, E=None, M=None, posdef=None, precond=None, max_niter=None, rtol=1e-
         rz_new = _coldot(r, z)
         p = z + (rz_new / _nonzero(rz, eps)) * p
         rz = rz_new
-    if trace is not None:
-        trace.update(niter=niter, napply=prob.napply, converged=converged, best_resid=best)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of best resid: %.3e" % (max_niter, best)))
-    return xbest
+    return _finish(xbest, prob, trace, converged, best, niter, max_niter, resid="best resid")
 
 
 def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, max_niter=None, rtol=1e-6, atol=1e-8,
@@ -199,14 +208,10 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
     """Stabilised bi-conjugate gradients in host memory (reference: bicgstab, solve.py:192-324); options as
     `native_krylov.bicgstab`."""
     calls["bicgstab"] += 1
-    if max_niter is None:
-        max_niter = int(1.5 * B.shape[-2])
-    bdims = _batchdims(A, B, E, M)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zero_solution(A, B, bdims)
-    prob = _HostProblem(A, B, E, M, bdims, posdef, need_hermit=False)
+    X0, prob, stop, max_niter = _setup(A, B, E, M, posdef, False, max_niter, rtol, atol, process_group)
+    if X0 is not None:
+        return X0
     pl, pr = _precond(precond_l), _precond(precond_r)
-    stop = _stop_of(prob, rtol, atol)
     x = torch.zeros(prob.shape, dtype=prob.dtype)
     r = prob.rhs
     r0 = r
@@ -247,12 +252,7 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
             converged = True
             break
         rho_old = rho
-    if trace is not None:
-        trace.update(niter=niter, napply=prob.napply, converged=converged, best_resid=best)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (max_niter, best)))
-    return xbest
+    return _finish(xbest, prob, trace, converged, best, niter, max_niter)
 
 
 def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-8, eps=1e-12, resid_calc_every=1,
@@ -266,14 +266,10 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     of all systems are one batched tensor; the small least-squares problem is `torch.linalg.lstsq`, as in the
     reference (:403).  `restart=m` (extension): GMRES(m), as in the native driver."""
     calls["gmres"] += 1
+    X0, prob, stop, max_niter = _setup(A, B, E, M, posdef, False, max_niter, rtol, atol, process_group, niter_factor=1)
+    if X0 is not None:
+        return X0
     nr = A.shape[-1]
-    if max_niter is None:
-        max_niter = int(nr)
-    bdims = _batchdims(A, B, E, M)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zero_solution(A, B, bdims)
-    prob = _HostProblem(A, B, E, M, bdims, posdef, need_hermit=False)
-    stop = _stop_of(prob, rtol, atol)
     msteps = min(nr, max_niter) - 1
     if restart is not None:
         restart = int(restart)
@@ -326,13 +322,7 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
             H.zero_()
             cyc0 = k + 1
             ncycles += 1
-    if trace is not None:
-        trace.update(niter=nsteps + 1, napply=prob.napply, converged=converged, best_resid=best, arnoldi_steps=nsteps,
-                     restarts=ncycles)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (max_niter, best)))
-    return xbest
+    return _finish(xbest, prob, trace, converged, best, nsteps + 1, max_niter, arnoldi_steps=nsteps, restarts=ncycles)
 
 
 def check_minres_inputs(A, M, E):
@@ -357,14 +347,10 @@ def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1
     replaced by the torch expression it computes.  The Lanczos / rotation scalars are float64 `(*batch, 1, ncols)`."""
     calls["minres"] += 1
     E = check_minres_inputs(A, M, E)
-    if max_niter is None:
-        max_niter = int(1.5 * A.shape[-1])
-    bdims = _batchdims(A, B, E, M)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zero_solution(A, B, bdims)
-    prob = _HostProblem(A, B, E, M, bdims, True, need_hermit=True)
+    X0, prob, stop, max_niter = _setup(A, B, E, M, True, True, max_niter, rtol, atol, process_group)
+    if X0 is not None:
+        return X0
     pre = _precond(precond)
-    stop = _stop_of(prob, rtol, atol)
     dt, f64 = prob.dtype, torch.float64
     one = torch.ones((*prob.bdims, 1, prob.nc), dtype=f64)
     safe = lambda d: torch.where(d == 0, one, d)
@@ -435,13 +421,7 @@ def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1
             break
         nrestart += 1
         r2 = rtrue
-    if trace is not None:
-        trace.update(niter=k, napply=prob.napply, converged=converged, best_resid=best, nrestart=nrestart,
-                     resid_history=hist)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (k, best)))
-    return x
+    return _finish(x, prob, trace, converged, best, k, k, nrestart=nrestart, resid_history=hist)
 
 
 def scipy_gmres(A, B, E=None, M=None, min_eps=1e-9, max_niter=None, **unused):

@@ -20,11 +20,12 @@ same algorithm in torch ops for operators in host memory.  Not built: an overlap
 converged columns.
 """
 import warnings
+from types import SimpleNamespace
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
 from xitorch_amd._util import ConvergenceWarning
-from xitorch_amd.linalg._panel import PanelOperator, pad_len
+from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, real_dtype, require_hip
+from xitorch_amd.linalg.native_krylov import _Kry
 from xitorch_amd.linalg import host_eig
 from xitorch_amd.linalg.host_eig import cheb_coefficients, cheb_default_nguard
 
@@ -93,7 +94,7 @@ class _ComplexBlock:
     def __init__(self, Bt, N, w, neig, dtype, device):
         self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
         self.ld = N
-        self.rdtype = torch.float64 if dtype == torch.complex128 else torch.float32
+        self.rdtype = real_dtype(dtype)
         self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
         self.status = torch.zeros((Bt + 1,), dtype=torch.float64, device=device)
         self.counts = {"rr_native": 0, "rr_library": 0}
@@ -178,18 +179,13 @@ def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
     """Ritz values and residual norm of a `steps`-step Lanczos run from one random vector per operator, all on the
     device: apply, xk_kry_dots for <v, A v> and |f|^2, xk_cheb_step for f = A v - alpha v - beta v_prev and for the
     normalisation.  Returns (theta (Bt, steps) of sign * A ascending, |f_k| (Bt,)) as float64 device tensors."""
-    cplx = dtype.is_complex
-    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
     ld = pad_len(N)
-    vn = {torch.float64: 2, torch.float32: 4, torch.complex128: 1, torch.complex64: 2}[dtype]
-    nblk = max(1, min(fn("xk_kry_max_partials")(), (N + 256 * vn * 4 - 1) // (256 * vn * 4)))
-    extra = (0,) if cplx else ()
+    kr = _Kry(SimpleNamespace(S=Bt, N=N, ld=ld, dtype=dtype, device=device))
 
     def dot(x, y):
-        P = torch.zeros((Bt, 64, 2) if cplx else (Bt, 64), dtype=rdt, device=device)
-        call("xk_kry_dots", dtype, ptr(x), ptr(y), ptr(None), ptr(None), ptr(None), ptr(None), ptr(P), ptr(None), Bt, N,
-             ld, nblk, *extra)
-        P = P[:, :nblk, 0] if cplx else P[:, :nblk]
+        P = kr.partial()
+        kr.dots(x, y, P)
+        P = P[:, :kr.nblk, 0] if kr.cplx else P[:, :kr.nblk]
         return P.to(torch.float64).sum(dim=1)
 
     bufs = [torch.zeros((Bt, 1, ld), dtype=dtype, device=device) for _ in range(3)]
@@ -268,17 +264,11 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
                                 V0=V0, v_init=v_init, rng_device=rng_device, lanczos_steps=lanczos_steps,
                                 verbose=verbose, trace=trace, process_group=process_group)
     host_eig._cheb_check_args("chebfsi", M, process_group)
-    if device.type != "cuda":
-        raise NativeLibraryError("xitorch_amd chebfsi runs on a HIP device only (operator is on %s)" % device)
+    require_hip(A, "chebfsi")
     dtype = A.dtype
-    if dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
-        raise NativeLibraryError("xitorch_amd chebfsi supports float64/float32 and complex128/complex64 operators, "
-                                 "got %s" % dtype)
     N = A.shape[-1]
     bdims = list(A.shape[:-2])
-    Bt = 1
-    for d in bdims:
-        Bt *= d
+    Bt = batch_count(bdims)
     if nguard is None:
         nguard = cheb_default_nguard(neig, N)
     w = min(N, neig + int(nguard))
@@ -289,7 +279,7 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
             trace.update(niter=0, napply=0, degree=degree, w=w, handed_to="exacteig")
         return exacteig(A, neig, mode, None)
     sign = 1.0 if mode == "lowest" else -1.0
-    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    rdt = real_dtype(dtype)
     blk = (_ComplexBlock if dtype.is_complex else _RealBlock)(Bt, N, w, neig, dtype, device)
     op = PanelOperator(A, bdims, Bt, N)
     if trace is not None and trace.get("k1_events") is not None:

@@ -31,7 +31,7 @@ import torch
 from xitorch_amd import kernels as K
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
-from xitorch_amd.linalg._panel import PanelOperator, pad_len
+from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, require_hip
 from xitorch_amd.dist import allreduce_max_
 
 __all__ = ["davidson", "exacteig", "take_eigpairs", "tallqr_extend", "native_partial_eigh"]
@@ -56,11 +56,11 @@ def take_eigpairs(evals, evecs, neig, mode):
     return evals[..., -neig:], evecs[..., -neig:]
 
 
-def _pad(n, dtype):
-    return pad_len(n)
-
-
-_PanelOperator = PanelOperator
+def _shift_rel(N, q, rdtype):
+    """first-pass shift of shifted CholeskyQR (Fukaya et al.), relative to trace(G): 11 (N q + q (q + 1)) u, capped, as
+    xk_davidson_orth chooses it"""
+    u = torch.finfo(rdtype).eps * 0.5
+    return min(11.0 * (N * q + q * (q + 1)) * u, 1e-3)
 
 
 def _gram(Vrows, k, panel, p, N):
@@ -208,8 +208,7 @@ class _Group:
             self.opM.apply(panel, self.MVs[:, k0:k0 + q])
             G = K.dense_mm(panel[:, :, :N], self.MVs[:, k0:k0 + q, :N])
         if shifted:
-            u = 1.1102230246251565e-16 if self.dtype == torch.float64 else 5.9604644775390625e-08
-            sh = min(1e-3, 11.0 * (float(N) * q + float(q) * (q + 1)) * u)
+            sh = _shift_rel(N, q, self.dtype)
             tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1)
             G = G + (sh * tr)[:, None, None] * torch.eye(q, dtype=G.dtype, device=G.device)
         Wq = self.Wflat[:self.B * q * q].view(self.B, q, q)      # compact (B, q, q), as the C ABI expects
@@ -439,7 +438,6 @@ class _Group:
         N, B = self.N, self.B
         bufs = [b for b in (self.Vs, self.AVs, self.MVs) if b is not None]
         coef_basis = self.Vs if self.opM is None else self.MVs
-        u = 1.1102230246251565e-16 if self.dtype == torch.float64 else 5.9604644775390625e-08
         k0 = 0
         while k0 < k:
             q = min(self.p if k0 > 0 else max(self.nguess0, 1), 32, k - k0)
@@ -453,7 +451,7 @@ class _Group:
                 G = K.dense_mm(panel[:, :, :N], Mp[:, :, :N])
                 G = (G + G.transpose(1, 2)) * 0.5
                 if it == 0:
-                    sh = min(1e-3, 11.0 * (float(N) * q + float(q) * (q + 1)) * u)
+                    sh = _shift_rel(N, q, self.dtype)
                     tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1)
                     G = G + (sh * tr)[:, None, None] * torch.eye(q, dtype=G.dtype, device=G.device)
                 Wq = torch.empty((B, q, q), dtype=self.dtype, device=self.device)
@@ -560,8 +558,8 @@ def tallqr_extend(V, t, M=None, orth_passes=2):
     B, N, k = V.shape
     p = t.shape[-1]
     dev, dtype = V.device, V.dtype
-    opM = _PanelOperator(M, [B], B, N) if M is not None else None
-    grp = _Group(None, opM, B, N, _pad(N, dtype), p, k, dtype, dev, "lowest", "native", orth_passes)
+    opM = PanelOperator(M, [B], B, N) if M is not None else None
+    grp = _Group(None, opM, B, N, pad_len(N), p, k, dtype, dev, "lowest", "native", orth_passes)
     grp.grow(k + p)
     grp.Vs[:, :k, :N].copy_(V.transpose(-2, -1))
     grp.Vs[:, k:k + p, :N].copy_(t.transpose(-2, -1))
@@ -783,7 +781,7 @@ def _plan_groups(A, whole, M, B, N, p, dtype, device, precond, overlap, groups, 
     if two:
         cuts = [(B * g) // ngrp for g in range(ngrp + 1)]
         spans = [(cuts[g], cuts[g + 1]) for g in range(ngrp)]
-        ops = [_PanelOperator(_sub_operator(A, B, N, b0, b1), [b1 - b0], b1 - b0, N) for (b0, b1) in spans]
+        ops = [PanelOperator(_sub_operator(A, B, N, b0, b1), [b1 - b0], b1 - b0, N) for (b0, b1) in spans]
         cur = torch.cuda.current_stream()
         # each group gets a stream with its own hardware queue (see kernels.masked_stream).  The caller's
         # stream is not used for a group: it usually is the legacy null stream, which synchronises implicitly
@@ -808,16 +806,16 @@ def _preconditioner(precond, whole, M, bdims, B, N, dtype, device):
         if precond.lower() not in ("diag", "jacobi", "davidson"):
             raise RuntimeError("Unknown davidson preconditioner: %s" % precond)
         dA = whole.diagonal()
-        dM = _PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
+        dM = PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
         return ("diag", dA, dM)
     if isinstance(precond, torch.Tensor):
         if precond.shape[-1] != N:
             raise RuntimeError("precond diagonal must have shape (*batch, %d), got %s" % (N, tuple(precond.shape)))
         dA = precond.to(device=device, dtype=dtype).expand(*bdims, N).reshape(B, N).contiguous()
-        dM = _PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
+        dM = PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
         return ("diag", dA, dM)
     if isinstance(precond, _LinOp):
-        return ("op", _PanelOperator(precond, bdims, B, N))
+        return ("op", PanelOperator(precond, bdims, B, N))
     raise TypeError("precond must be None, 'diag', a tensor or a LinearOperator, got %s" % type(precond))
 
 
@@ -954,9 +952,8 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
         return host_eig.davidson(A, neig, mode, M, max_niter=max_niter, nguess=nguess, v_init=v_init,
                                  max_addition=max_addition, min_eps=min_eps, verbose=verbose, V0=V0,
                                  process_group=process_group, trace=trace, precond=precond, restart=restart)
-    if device.type != "cuda":
-        raise NativeLibraryError("xitorch_amd davidson runs on a HIP device only (operator is on %s)" % device)
-    if dtype in (torch.complex128, torch.complex64):
+    require_hip(A, "davidson")
+    if dtype.is_complex:
         # complex Hermitian operators: the same iteration on the complex kernels (native_eig_herm.py); the reference's
         # davidson is real-only (unconjugated transposes, symeig.py:163)
         from xitorch_amd.linalg import native_eig_herm
@@ -964,13 +961,8 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
                                         max_addition=max_addition, min_eps=min_eps, verbose=verbose, V0=V0,
                                         process_group=process_group, trace=trace, rng_device=rng_device,
                                         precond=precond, restart=restart)
-    if dtype not in (torch.float64, torch.float32):
-        raise NativeLibraryError("xitorch_amd davidson supports float64/float32 and complex128/complex64 operators, "
-                                 "got %s" % dtype)
-    B = 1
-    for d in bdims:
-        B *= d
-    N, Npad = na, _pad(na, dtype)
+    B = batch_count(bdims)
+    N, Npad = na, pad_len(na)
     p = neig
     if restart is not None:
         restart = int(restart)
@@ -985,7 +977,7 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
     events = trace.get("k1_events") if trace is not None else None
 
     # ---- batch groups: one, or two pipelined on their own streams (policy: `_plan_groups`) --------------------------
-    whole = _PanelOperator(A, bdims, B, N)
+    whole = PanelOperator(A, bdims, B, N)
     plan = _plan_groups(A, whole, M, B, N, p, dtype, device, precond, overlap, groups, reserve_cus, k1_streams,
                         ([(0, int(reserve_early[0])), (int(reserve_early[1]), None)] if reserve_early is not None
                          else reserve_schedule), process_group)
@@ -1006,7 +998,7 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
     groups = []
     for g, (b0, b1) in enumerate(spans):
         with torch.cuda.stream(streams[g]):
-            opM = _PanelOperator(M, bdims, B, N) if M is not None else None
+            opM = PanelOperator(M, bdims, B, N) if M is not None else None
             grp = _Group(ops[g], opM, b1 - b0, N, Npad, p, nguess, dtype, device, mode, small_eigh, orth_passes,
                          precond=_pc_slice(pc_full, b0, b1), restart=restart, capacity=basis_capacity)
             grp.k1_stream = k1_streams[g]

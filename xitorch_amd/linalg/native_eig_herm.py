@@ -17,7 +17,8 @@ import torch
 from xitorch_amd import kernels as K
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
-from xitorch_amd.linalg._panel import PanelOperator
+from xitorch_amd.linalg._panel import PanelOperator, batch_count, real_dtype, require_hip
+from xitorch_amd.linalg.native_eig import _initial_block, _shift_rel
 
 __all__ = ["davidson", "herm_partial_eigh"]
 
@@ -63,12 +64,6 @@ def _combine(Vk, C):
     return K.dense_mm_complex(Vk, C.transpose(1, 2).contiguous(), adjoint=True, conj_io=True)
 
 
-def _shift_rel(N, q, dtype):
-    """first-pass shift of shifted CholeskyQR (Fukaya et al.), as xk_davidson_orth chooses it"""
-    u = torch.finfo(dtype).eps * 0.5
-    return min(11.0 * (N * q + q * (q + 1)) * u, 1e-3)
-
-
 class _Basis:
     """V, A V (and M V) in (B, cap, N) panel-major device buffers, T in (B, cap, cap); capacity doubled on demand."""
 
@@ -105,12 +100,10 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
     """Block Davidson for a complex Hermitian operator on a HIP device; options as `native_eig.davidson`.  The
     scheduling options of the real pipeline are accepted and ignored; `precond=`, `restart=` and batch sharding over
     several ranks are not available for complex operators."""
-    from xitorch_amd.linalg.native_eig import _initial_block
     dtype, device = A.dtype, torch.device(A.device)
-    if dtype not in (torch.complex128, torch.complex64):
+    require_hip(A, "davidson")
+    if not dtype.is_complex:
         raise NativeLibraryError("native_eig_herm serves complex128 / complex64 operators, got %s" % dtype)
-    if device.type != "cuda":
-        raise NativeLibraryError("native_eig_herm runs on a HIP device only (operator is on %s)" % device)
     if precond is not None or restart is not None:
         raise NativeLibraryError("precond= / restart= are not available for complex Hermitian operators: the native "
                                  "extension (xk_herm_davidson) has no preconditioned or restarted form")
@@ -128,10 +121,8 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
         raise NativeLibraryError("neig / nguess > %d is not supported by the native complex davidson (block width of "
                                  "xk_herm_cholqr)" % K.HERM_CHOLQR_MAX_Q)
     bdims = list(A.shape[:-2]) if M is None else list(bcast_shape(A.shape[:-2], M.shape[:-2]))
-    B = 1
-    for d in bdims:
-        B *= d
-    rdtype = torch.float64 if dtype == torch.complex128 else torch.float32
+    B = batch_count(bdims)
+    rdtype = real_dtype(dtype)
     opA = PanelOperator(A, bdims, B, N)
     opM = PanelOperator(M, bdims, B, N) if M is not None else None
     counts = {"rr_native": 0, "rr_library": 0}

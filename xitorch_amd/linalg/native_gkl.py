@@ -8,7 +8,7 @@ on the long side the null space of A pollutes the small Ritz values and mode="lo
 One Lanczos step j:
   u_j = A v_j, orthogonalised against U[:j]     -> alpha_j = |u_j|, stored straight into the projected matrix Bm[j, j]
   v_{j+1} = A^H u_j, orthogonalised against V[:j+1] -> beta_j = |v_{j+1}|, stored into Bm[j, j+1] (the last one apart)
-Each half: one rectangular apply (`_RectOperator`: dense through `trans`, CSR on its CSC view, banded, or the operator's
+Each half: one rectangular apply (`RectPanelOperator`: dense through `trans`, CSR on its CSC view, banded, or the operator's
 own .mm / .rmm) into the vector's basis slot, then CGS2 in THREE xk_gkl_sweep passes over the basis (accumulate / apply
 and accumulate / apply and take the norm) with an xk_gkl_finish after each, and a fourth, basis-free sweep that scales
 the slot by 1 / norm.  Nothing is read by the host inside a cycle.  At the end of a cycle xk_gkl_bsvd takes the SVD of
@@ -30,77 +30,11 @@ block is the one returned).  `host_eig.gkl` is the same algorithm in torch ops f
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import ConvergenceWarning
-from xitorch_amd.linalg._panel import pad_len
+from xitorch_amd.linalg._panel import RectPanelOperator, pad_len, batch_count, real_dtype, require_hip
 from xitorch_amd.linalg import host_eig
 
 __all__ = ["gkl"]
-
-
-class _RectOperator:
-    """Panel apply of a rectangular operator (*BA, m, n): out[:, :, :m] = A x[:, :, :n] or out[:, :, :n] = A^H x[:, :, :m]
-    on (Bt, p, ld) panels, without layout copies for the native operator kinds (the kernels `PanelOperator` uses, with
-    separate in and out lengths)."""
-
-    def __init__(self, A, bdims, Bt):
-        from xitorch_amd.linop import MatrixLinearOperator, BandedLinearOperator, SparseLinearOperator
-        self.A, self.bdims, self.Bt = A, list(bdims), Bt
-        self.m, self.n = A.shape[-2], A.shape[-1]
-        self.kind = "generic"
-        self.napply = 0
-        self.torch_applies = 0      # applies served by the operator's own torch expression (.mm / .rmm)
-        nA = 1
-        for d in A.shape[:-2]:
-            nA *= d
-        real = lambda t: t.is_cuda and t.dtype in (torch.float64, torch.float32)
-        cplx = lambda t: t.is_cuda and t.dtype in (torch.complex128, torch.complex64)
-        self.cplx, self.cj, self.flip = False, False, False
-        if isinstance(A, MatrixLinearOperator) and (real(A.mat) or cplx(A.mat)) and (nA == Bt or nA == 1):
-            mat = A.mat
-            if cplx(mat):
-                self.cplx = True
-                if mat.is_conj():
-                    mat, self.cj = mat.conj(), True
-            flip = False
-            if mat.dim() >= 2 and mat.stride(-1) != 1 and mat.stride(-2) == 1:
-                mat, flip = mat.transpose(-2, -1), True                   # a transposed view (e.g. A.H)
-            if mat.is_contiguous() or mat.dim() == 2 and mat.stride(-1) == 1:
-                self.kind, self.flip = "dense", flip
-                self.mat = mat.reshape(nA, *mat.shape[-2:]) if mat.dim() > 2 else mat
-        elif isinstance(A, BandedLinearOperator) and real(A.band) and (nA == Bt or nA == 1) and A.band.is_contiguous():
-            self.kind = "banded"
-            self.band = A.band.reshape(nA, *A.band.shape[-2:])
-        elif isinstance(A, SparseLinearOperator) and (real(A.values) or cplx(A.values)) and (nA == Bt or nA == 1):
-            self.kind = "csr"
-            self.cplx = cplx(A.values)
-            self.pat = A._pattern
-            self.vals = A.values.resolve_conj().reshape(-1, A.nnz)
-            if A.nnz > 1 and self.vals.stride(-1) != 1:
-                self.vals = self.vals.contiguous()
-
-    def apply(self, X, out, adjoint):
-        """X, out: (Bt, p, ld) panels; adjoint False: out[..., :m] = A X[..., :n]; True: out[..., :n] = A^H X[..., :m]"""
-        self.napply += 1
-        nin, nout = (self.m, self.n) if adjoint else (self.n, self.m)
-        Xn, On = X[:, :, :nin], out[:, :, :nout]
-        if self.kind == "dense" and self.cplx:
-            # stored matrix S, operator = S / S^T / conj(S) / S^H by (flip, cj), as in PanelOperator
-            K.dense_mm_complex(self.mat if self.mat.dim() == 3 else self.mat.unsqueeze(0), Xn,
-                               adjoint=(self.flip != adjoint), conj_io=(self.flip != self.cj), out=On)
-        elif self.kind == "dense":
-            K.dense_mm(self.mat, Xn, out=On, trans=(adjoint != self.flip))
-        elif self.kind == "csr":
-            K.csr_mm(self.pat, self.vals, Xn, out=On, trans=adjoint)
-        elif self.kind == "banded":
-            K.banded_mm(self.band, Xn, out=On, trans=adjoint)
-        else:
-            self.torch_applies += 1
-            p = X.shape[1]
-            x = Xn.transpose(-2, -1).reshape(*self.bdims, nin, p)
-            y = self.A.rmm(x) if adjoint else self.A.mm(x)
-            On.copy_(y.expand(*self.bdims, nout, p).reshape(self.Bt, nout, p).transpose(-2, -1))
-        return out
 
 
 class _Side:
@@ -121,7 +55,7 @@ class _State:
     def __init__(self, Bt, ncv, mm, nn, dtype, device):
         f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=device)
         self.Bt, self.ncv, self.dtype, self.device = Bt, ncv, dtype, device
-        self.rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+        self.rdt = real_dtype(dtype)
         self.u_round = float(torch.finfo(self.rdt).eps)
         self.U = _Side(Bt, ncv, mm, dtype, device)
         self.V = _Side(Bt, ncv + 1, nn, dtype, device)
@@ -205,21 +139,15 @@ def gkl(A, k, mode, max_niter=100, min_eps=1e-6, ncv=None, V0=None, v_init="rand
         return host_eig.gkl(A, k, mode, max_niter=max_niter, min_eps=min_eps, ncv=ncv, V0=V0, v_init=v_init,
                             rng_device=rng_device, verbose=verbose, trace=trace, process_group=process_group)
     m, n, tall, mm, nn, k, ncv, keep, dense = host_eig._gkl_setup(A, k, mode, ncv, process_group)
-    if device.type != "cuda":
-        raise NativeLibraryError("xitorch_amd gkl runs on a HIP device only (operator is on %s)" % device)
+    require_hip(A, "gkl")
     dtype = A.dtype
-    if dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
-        raise NativeLibraryError("xitorch_amd gkl supports float64/float32 and complex128/complex64 operators, got %s"
-                                 % dtype)
     if dense:
         if trace is not None:
             trace.update(niter=0, napply=0, ncv=ncv, handed_to="dense_svd")
         return host_eig._gkl_dense(A, k, mode)
     bdims = list(A.shape[:-2])
-    Bt = 1
-    for d in bdims:
-        Bt *= d
-    op = _RectOperator(A, bdims, Bt)
+    Bt = batch_count(bdims)
+    op = RectPanelOperator(A, bdims, Bt)
     st = _State(Bt, ncv, mm, nn, dtype, device)
     U, V = st.U, st.V
     descending = mode != "lowest"
@@ -234,10 +162,10 @@ def gkl(A, k, mode, max_niter=100, min_eps=1e-6, ncv=None, V0=None, v_init="rand
     def half_step(h):
         j = h // 2
         if h % 2 == 0:
-            op.apply(V.panel[:, j:j + 1], U.panel[:, j:j + 1], adjoint=not tall)
+            op.apply(V.panel[:, j:j + 1], U.panel[:, j:j + 1], trans=not tall)
             st.orthonormalise(U, j, dst=st.Bm[:, j, j], code=h)
         else:
-            op.apply(U.panel[:, j:j + 1], V.panel[:, j + 1:j + 2], adjoint=tall)
+            op.apply(U.panel[:, j:j + 1], V.panel[:, j + 1:j + 2], trans=tall)
             st.orthonormalise(V, j + 1, dst=st.Bm[:, j, j + 1] if j + 1 < ncv else st.beta, code=h)
 
     def recover(h, members):

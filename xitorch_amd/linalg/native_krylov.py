@@ -17,9 +17,12 @@ Q11); here the shift is simply a per-system scalar.
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
-from xitorch_amd._util import bcast_shape, pad_shapes, ConvergenceWarning
-from xitorch_amd.linalg._panel import PanelOperator, pad_len, to_panel, from_panel
+from xitorch_amd._capi import NativeLibraryError, ptr, call
+from xitorch_amd._util import pad_shapes, ConvergenceWarning
+from xitorch_amd.linalg import host_krylov
+from xitorch_amd.linalg.host_krylov import get_batchdims, zero_solution
+from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, real_dtype, kry_blocks, require_hip, \
+    to_panel, from_panel
 from xitorch_amd.dist import allreduce_max_, all_ranks_agree_true
 
 __all__ = ["exactsolve", "custom_exactsolve", "cg", "bicgstab", "gmres", "minres", "scipy_gmres", "broyden1_solve", "get_batchdims"]
@@ -30,16 +33,6 @@ def _in_host_memory(A):
     are served by host_krylov.py; everything else — any device tensor — by the HIP kernels below and by nothing else:
     `_Problem` raises for a device it has no kernels for, `_capi.lib()` raises when the library is missing."""
     return torch.device(A.device).type == "cpu"
-
-
-def get_batchdims(A, B, E, M):
-    """Broadcast batch shape of the solution (reference: _get_batchdims, solve.py:540-549)."""
-    shapes = [A.shape[:-2], B.shape[:-2]]
-    if E is not None:
-        shapes.append(E.shape[:-1])
-        if M is not None:
-            shapes.append(M.shape[:-2])
-    return bcast_shape(*shapes)
 
 
 # ------------------------------------------------------------------------------- dense
@@ -85,23 +78,14 @@ class _Problem:
     equations (reference: _setup_linear_problem, solve.py:560-643)."""
 
     def __init__(self, A, B, E, M, bdims, posdef, need_hermit):
-        dev = torch.device(A.device)
-        if dev.type != "cuda":
-            raise NativeLibraryError("xitorch_amd native solvers run on a HIP device only (operator is on %s)" % dev)
-        if A.dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
-            raise NativeLibraryError("xitorch_amd native solvers support float64/float32/complex128/complex64, "
-                                     "got %s" % A.dtype)
-        self.dtype, self.device = A.dtype, dev
+        require_hip(A, "native solvers")
+        self.dtype, self.device = A.dtype, torch.device(A.device)
         self.cplx = A.dtype.is_complex
-        # element type of the kernels' scalars / partials, and complex elements per 16 B vector (block sizing)
-        self.rdtype = {torch.complex128: torch.float64, torch.complex64: torch.float32}.get(A.dtype, A.dtype)
-        self.vec_elems = {torch.float64: 2, torch.float32: 4, torch.complex128: 1, torch.complex64: 2}[A.dtype]
+        self.rdtype = real_dtype(A.dtype)         # element type of the kernels' scalars / partials
         self.bdims = list(bdims)
         self.N = A.shape[-1]
         self.nc = B.shape[-1]
-        self.Bt = 1
-        for d in self.bdims:
-            self.Bt *= d
+        self.Bt = batch_count(self.bdims)
         self.ld = pad_len(self.N)
         self.S = self.Bt * self.nc
         self.opA = PanelOperator(A, self.bdims, self.Bt, self.N)
@@ -112,6 +96,7 @@ class _Problem:
         self._tmp = None
         self._tmp2 = None
         self._scratchP = None
+        self.kr = _Kry(self)
         rhs = to_panel(B.to(self.dtype), self.bdims, self.Bt, self.N)
 
         hermit = A.is_hermitian and (M is None or M.is_hermitian)
@@ -139,16 +124,13 @@ class _Problem:
         return self._tmp2
 
     def nblk(self):
-        vn = self.vec_elems
-        return max(1, min(fn("xk_kry_max_partials")(), (self.N + 256 * vn * 4 - 1) // (256 * vn * 4)))
+        return kry_blocks(self.N, self.dtype)
 
     def _shift_now(self, out, Z):
         """out -= E * Z in place through xk_kry_dots' shift stage (its dot product goes to a scratch partial)."""
         if self._scratchP is None:
-            self._scratchP = torch.zeros((self.S, 64, 2 if self.cplx else 1), dtype=self.rdtype, device=self.device)
-        extra = (0,) if self.cplx else ()
-        call("xk_kry_dots", self.dtype, ptr(out), ptr(out), ptr(None), ptr(None), ptr(Z), ptr(self.E),
-             ptr(self._scratchP), ptr(None), self.S, self.N, self.ld, self.nblk(), *extra)
+            self._scratchP = self.kr.partial()
+        self.kr.dots(out, out, self._scratchP, shift=Z)
 
     def _apply1(self, X, out, trans=False, defer=False):
         """out = A X - E * (M X)  (solve.py:590-604).  defer=True leaves the shift to the caller's next
@@ -212,16 +194,19 @@ class _Problem:
 
 
 class _Kry:
-    """ctypes plumbing of the fused Krylov kernels on (S, ld) arrays (real or interleaved complex)."""
+    """ctypes plumbing of the fused Krylov kernels on (S, ld) arrays (real or interleaved complex): S systems of
+    length N and pitch ld, as any object with `S, N, ld, dtype, device` (and `E`, the per-system shifts, when `dots`
+    is to fold them in) describes them.  `nblk` is the block count the kernels are launched with: `geom.nblk()` where
+    the object has its own (a `_Problem`), else `kry_blocks(N, dtype)`."""
 
-    def __init__(self, prob):
-        self.S, self.N, self.ld = prob.S, prob.N, prob.ld
-        self.cplx = prob.cplx
-        self.nblk = prob.nblk()
-        self.dtype, self.rdtype, self.device = prob.dtype, prob.rdtype, prob.device
-        self.E = prob.E
-        self.status = torch.zeros((2,), dtype=torch.float64, device=prob.device)
-        self.rnorm = torch.zeros((prob.S,), dtype=prob.rdtype, device=prob.device)
+    def __init__(self, geom):
+        self.S, self.N, self.ld = geom.S, geom.N, geom.ld
+        self.dtype, self.device = geom.dtype, geom.device
+        self.cplx, self.rdtype = geom.dtype.is_complex, real_dtype(geom.dtype)
+        self.nblk = geom.nblk() if hasattr(geom, "nblk") else kry_blocks(geom.N, geom.dtype)
+        self.E = getattr(geom, "E", None)
+        self.status = torch.zeros((2,), dtype=torch.float64, device=self.device)
+        self.rnorm = torch.zeros((self.S,), dtype=self.rdtype, device=self.device)
 
     def partial(self):
         """block partials of an inner product: (S, 64) real, or (S, 64, 2) for complex products"""
@@ -262,15 +247,11 @@ class _Kry:
 
     def resid(self, b, y, r, r0, Prr, Prho, init=False):
         """r = b - y with partials |r|^2 -> Prr (real) and <r0, r> -> Prho; init=True: only the partials of the
-        vector `b` itself (y is taken as zero: the kernel is run with y = a zero panel once)."""
+        vector `b` itself (y is taken as zero: the kernel is run with y = a zero panel and a scratch r)."""
         if init:
             if getattr(self, "_zero", None) is None or self._zero.shape != b.shape:
                 self._zero = torch.zeros_like(b)
-            self._scr = torch.empty_like(b)
-            call("xk_kry_resid", self.dtype, ptr(b), ptr(self._zero), ptr(self._scr), ptr(r0), ptr(Prr), ptr(Prho),
-                 self.S, self.N, self.ld, self.nblk)
-            self._scr = None
-            return
+            y, r = self._zero, torch.empty_like(b)
         call("xk_kry_resid", self.dtype, ptr(b), ptr(y), ptr(r), ptr(r0), ptr(Prr), ptr(Prho), self.S, self.N, self.ld,
              self.nblk)
 
@@ -293,13 +274,40 @@ class _Kry:
         return mx, nbad
 
 
-def _zeros_like_solution(A, B, bdims):
-    return torch.zeros((*bdims, A.shape[-1], B.shape[-1]), dtype=A.dtype, device=A.device)
+class _Run:
+    """What cg / bicgstab / gmres / minres share around their loops.  Before: device dispatch (an operator in host
+    memory goes to the method of the same name in host_krylov.py), the `max_niter` default, the zero right-hand side
+    shortcut, the problem in panel layout with its kernels and the stopping vector.  After: the trace, the warning and
+    the solution in the caller's layout.  `X` is the result when there is nothing (left) to iterate on, else None."""
 
+    def __init__(self, method, A, B, E, M, opt, posdef, need_hermit, niter_factor=1.5):
+        self.X = self.prob = None
+        if _in_host_memory(A):
+            self.X = getattr(host_krylov, method)(A, B, E, M, **opt)
+            return
+        self.trace, self.process_group = opt["trace"], opt["process_group"]
+        self.max_niter = int(niter_factor * A.shape[-1]) if opt["max_niter"] is None else opt["max_niter"]
+        bdims = get_batchdims(A, B, E, M)
+        # (sharded runs: every rank takes this shortcut or none does — the loops contain collectives)
+        if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=opt["rtol"], atol=opt["atol"]), B.device,
+                                self.process_group):
+            self.X = zero_solution(A, B, bdims)
+            return
+        self.prob = _Problem(A, B, E, M, bdims, posdef, need_hermit)
+        if self.trace is not None and self.trace.get("k1_events") is not None:
+            self.prob.opA.events = self.trace["k1_events"]      # measurement: HIP events around every operator apply
+        self.kr = self.prob.kr
+        bnorm = self.prob.rhs.norm(dim=-1).reshape(-1)
+        self.stop = torch.max(opt["rtol"] * bnorm, opt["atol"] * torch.ones_like(bnorm)).contiguous()
 
-def _stop_vector(prob, rtol, atol):
-    bnorm = prob.rhs.norm(dim=-1).reshape(-1)
-    return torch.max(rtol * bnorm, atol * torch.ones_like(bnorm)).contiguous()
+    def finish(self, Xp, converged, best, niter, said_niter, resid="resid", **more):
+        """Xp: the panel of the iterate to return"""
+        if self.trace is not None:
+            self.trace.update(niter=niter, napply=self.prob.napply, converged=converged, best_resid=best, **more)
+        if not converged:
+            warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
+                                             "Max norm of %s: %.3e" % (said_niter, resid, best)))
+        return self.prob.solution(Xp)
 
 
 def _precond(P, prob):
@@ -353,24 +361,13 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
     process_group: torch.distributed group or None
         (extension) batch-sharded multi-GPU run: the stopping test is all-reduced over the group
     """
-    if _in_host_memory(A):
-        from xitorch_amd.linalg import host_krylov
-        return host_krylov.bicgstab(A, B, E, M, posdef=posdef, precond_l=precond_l, precond_r=precond_r,
-                                    max_niter=max_niter, rtol=rtol, atol=atol, eps=eps, verbose=verbose,
-                                    resid_calc_every=resid_calc_every, process_group=process_group, trace=trace)
-    nr, ncols = B.shape[-2:]
-    if max_niter is None:
-        max_niter = int(1.5 * nr)
-    bdims = get_batchdims(A, B, E, M)
-    # (sharded runs: every rank takes this shortcut or none does — the loop below contains collectives)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zeros_like_solution(A, B, bdims)
-    prob = _Problem(A, B, E, M, bdims, posdef, need_hermit=False)
-    if trace is not None and trace.get("k1_events") is not None:
-        prob.opA.events = trace["k1_events"]          # measurement: HIP events around every operator apply
-    kr = _Kry(prob)
+    run = _Run("bicgstab", A, B, E, M, dict(
+        posdef=posdef, precond_l=precond_l, precond_r=precond_r, max_niter=max_niter, rtol=rtol, atol=atol, eps=eps,
+        verbose=verbose, resid_calc_every=resid_calc_every, process_group=process_group, trace=trace), posdef, False)
+    if run.X is not None:
+        return run.X
+    prob, kr, stop, max_niter = run.prob, run.kr, run.stop, run.max_niter
     pl, pr = _precond(precond_l, prob), _precond(precond_r, prob)
-    stop = _stop_vector(prob, rtol, atol)
 
     r = prob.rhs.clone()                      # x0 = 0  ->  r = B - A 0 = B (solve.py:262)
     r0 = r.clone()
@@ -421,12 +418,7 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
         if nbad == 0:
             converged = True
             break
-    if trace is not None:
-        trace.update(niter=niter, napply=prob.napply, converged=converged, best_resid=best)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (max_niter, best)))
-    return prob.solution(ring.bufs[ring.best])
+    return run.finish(ring.bufs[ring.best], converged, best, niter, max_niter)
 
 
 # ------------------------------------------------------------------------------- CG
@@ -456,25 +448,13 @@ def cg(A, B, E=None, M=None, posdef=None, precond=None, max_niter=None, rtol=1e-
     process_group: torch.distributed group or None
         (extension) batch-sharded multi-GPU run: the stopping test is all-reduced over the group
     """
-    if _in_host_memory(A):
-        from xitorch_amd.linalg import host_krylov
-        return host_krylov.cg(A, B, E, M, posdef=posdef, precond=precond, max_niter=max_niter, rtol=rtol, atol=atol,
-                              eps=eps, resid_calc_every=resid_calc_every, verbose=verbose,
-                              process_group=process_group, trace=trace)
-    nr = A.shape[-1]
-    ncols = B.shape[-1]
-    if max_niter is None:
-        max_niter = int(1.5 * nr)
-    bdims = get_batchdims(A, B, E, M)
-    # (sharded runs: every rank takes this shortcut or none does — the loop below contains collectives)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zeros_like_solution(A, B, bdims)
-    prob = _Problem(A, B, E, M, bdims, posdef, need_hermit=True)
-    if trace is not None and trace.get("k1_events") is not None:
-        prob.opA.events = trace["k1_events"]          # measurement: HIP events around every operator apply
-    kr = _Kry(prob)
+    run = _Run("cg", A, B, E, M, dict(
+        posdef=posdef, precond=precond, max_niter=max_niter, rtol=rtol, atol=atol, eps=eps,
+        resid_calc_every=resid_calc_every, verbose=verbose, process_group=process_group, trace=trace), posdef, True)
+    if run.X is not None:
+        return run.X
+    prob, kr, stop, max_niter = run.prob, run.kr, run.stop, run.max_niter
     pre = _precond(precond, prob)
-    stop = _stop_vector(prob, rtol, atol)
 
     r = prob.rhs.clone()
     z = prob.new() if pre is not None else r
@@ -515,40 +495,40 @@ def cg(A, B, E=None, M=None, posdef=None, precond=None, max_niter=None, rtol=1e-
         kr.dots(r, z, Prz[1 - cur])
         kr.cg_p(z, p, Prz[1 - cur], Prz[cur], eps)
         cur = 1 - cur
-    if trace is not None:
-        trace.update(niter=niter, napply=prob.napply, converged=converged, best_resid=best)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of best resid: %.3e" % (max_niter, best)))
-    return prob.solution(ring.bufs[ring.best])
+    return run.finish(ring.bufs[ring.best], converged, best, niter, max_niter, resid="best resid")
 
 
 # ------------------------------------------------------------------------------- GMRES
 class _GmresState:
-    """Per-system Hessenberg / Givens state on the device (float64 whatever the vector dtype), growing with the basis
-    (the reference preallocates max_niter vectors and a (max_niter+1) x max_niter Hessenberg, solve.py:384-386, Q12).
-    cplx: R, sn, g are complex128 (interleaved pairs for xk_gmres_*_c*), cs stays real."""
+    """Everything of GMRES that grows with the Krylov basis, on the device: the basis Q (S, cap, ld) and the coefficient
+    row `ycoef` of the iterate in the vector dtype; the per-system Hessenberg / Givens state R, cs, sn, g for cap - 1
+    columns (float64 whatever the vector dtype; complex: R, sn, g are complex128, interleaved pairs for
+    xk_gmres_*_c*, cs stays real); complex only, the coefficient rows c1, c2n of the two Gram passes and the scratch of
+    xk_gmres_gram_c*' fixed-shape reduction, one double pair per (system, tile, row).  (The reference preallocates
+    max_niter vectors and a (max_niter+1) x max_niter Hessenberg, solve.py:384-386, Q12.)"""
 
-    def __init__(self, S, cap, device, cplx=False):
-        self.S, self.cap, self.device = S, cap, device
-        self.zdtype = torch.complex128 if cplx else torch.float64
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-        if cplx:
-            zc = lambda *shape: torch.zeros(shape, dtype=torch.complex128, device=device)
-            self.R, self.cs, self.sn, self.g = zc(S, cap + 1, cap), z(S, cap), zc(S, cap), zc(S, cap + 1)
-            return
-        self.R, self.cs, self.sn, self.g = z(S, cap + 1, cap), z(S, cap), z(S, cap), z(S, cap + 1)
+    def __init__(self, S, N, ld, dtype, device, cap):
+        self.S, self.ld, self.dtype, self.device = S, ld, dtype, device
+        self.gtiles = K.gmres_gram_tiles(N, dtype) if dtype.is_complex else 0
+        self.cap = 0
+        self.grow(cap)
 
-    def grow(self, need, limit):
-        if need <= self.cap:
-            return
-        new = min(limit, max(need, 2 * self.cap))
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
-        zc = lambda *shape: torch.zeros(shape, dtype=self.zdtype, device=self.device)
-        R, cs, sn, g = zc(self.S, new + 1, new), z(self.S, new), zc(self.S, new), zc(self.S, new + 1)
-        R[:, :self.cap + 1, :self.cap] = self.R
-        cs[:, :self.cap], sn[:, :self.cap], g[:, :self.cap + 1] = self.cs, self.sn, self.g
-        self.R, self.cs, self.sn, self.g, self.cap = R, cs, sn, g, new
+    def grow(self, cap):
+        """storage for `cap` basis vectors, the first `self.cap` kept"""
+        S, old, hc, ho = self.S, self.cap, cap - 1, self.cap - 1
+        zdtype = torch.complex128 if self.dtype.is_complex else torch.float64
+        z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
+        Q = z(self.dtype, S, cap, self.ld)
+        R, cs, sn, g = z(zdtype, S, hc + 1, hc), z(torch.float64, S, hc), z(zdtype, S, hc), z(zdtype, S, hc + 1)
+        if old:
+            Q[:, :old].copy_(self.Q)
+            R[:, :ho + 1, :ho] = self.R
+            cs[:, :ho], sn[:, :ho], g[:, :ho + 1] = self.cs, self.sn, self.g
+        self.Q, self.R, self.cs, self.sn, self.g, self.cap, self.hcap = Q, R, cs, sn, g, cap, hc
+        self.ycoef = z(self.dtype, S, 1, cap)
+        if self.dtype.is_complex:
+            self.c1, self.c2n = z(self.dtype, S, cap + 1), z(self.dtype, S, cap + 1)
+            self.gscr = z(torch.float64, S * self.gtiles * (cap + 1) * 2)
 
 
 def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-8, eps=1e-12,
@@ -606,25 +586,15 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     swap (:432, and fails for more than one column); this function returns ``(*batch, nr, ncols)`` like every other
     method.
     """
-    if _in_host_memory(A):
-        from xitorch_amd.linalg import host_krylov
-        return host_krylov.gmres(A, B, E, M, posdef=posdef, max_niter=max_niter, rtol=rtol, atol=atol, eps=eps,
-                                 resid_calc_every=resid_calc_every, restart=restart, process_group=process_group,
-                                 trace=trace)
-    nr, ncols = A.shape[-1], B.shape[-1]
-    if max_niter is None:
-        max_niter = int(nr)
-    bdims = get_batchdims(A, B, E, M)
-    # (sharded runs: every rank takes this shortcut or none does — the loop below contains collectives)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zeros_like_solution(A, B, bdims)
-    prob = _Problem(A, B, E, M, bdims, posdef, need_hermit=False)
-    if trace is not None and trace.get("k1_events") is not None:
-        prob.opA.events = trace["k1_events"]          # measurement: HIP events around every operator apply
-    kr = _Kry(prob)
+    run = _Run("gmres", A, B, E, M, dict(
+        posdef=posdef, max_niter=max_niter, rtol=rtol, atol=atol, eps=eps, resid_calc_every=resid_calc_every,
+        restart=restart, process_group=process_group, trace=trace), posdef, False, niter_factor=1)
+    if run.X is not None:
+        return run.X
+    prob, kr, stop, max_niter = run.prob, run.kr, run.stop, run.max_niter
+    nr = A.shape[-1]
     S, N, ld = prob.S, prob.N, prob.ld
     dtype, dev = prob.dtype, prob.device
-    stop = _stop_vector(prob, rtol, atol)
     every = max(1, int(resid_calc_every))
     msteps = min(nr, max_niter) - 1           # Arnoldi steps whose column enters an iterate (solve.py:389,403)
     if restart is not None:
@@ -652,22 +622,12 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     converged = False
     nsteps, nsync, ncycles = 0, 1, 0
     if msteps > 0:
-        cap = min(mcyc + 1, 32)
         x_base = None                         # restarted cycles: the iterate the current cycle corrects
-        Q = torch.zeros((S, cap, ld), dtype=dtype, device=dev)
-        Q[:, 0] = rhs / torch.where(beta == 0, torch.full_like(beta, eps), beta).unsqueeze(-1)   # :385, _safedenom
-        st = _GmresState(S, cap - 1, dev, cplx=prob.cplx)
+        st = _GmresState(S, N, ld, dtype, dev, min(mcyc + 1, 32))
+        st.Q[:, 0] = rhs / torch.where(beta == 0, torch.full_like(beta, eps), beta).unsqueeze(-1)   # :385, _safedenom
         st.g[:, 0] = beta.double()
         inv_hn = torch.zeros((S,), dtype=prob.rdtype, device=dev)
-        if prob.cplx:
-            # complex: the two Gram passes write into (S, cap + 1) coefficient rows; the fixed-shape reduction of
-            # xk_gmres_gram_c* wants one double pair per (system, tile, row) of scratch
-            gtiles = K.gmres_gram_tiles(N, dtype)
-            c1 = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
-            c2n = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
-            gscr = torch.zeros((S * gtiles * (cap + 1) * 2,), dtype=torch.float64, device=dev)
         Pest, Ptrue = kr.partial_real(), kr.partial_real()
-        ycoef = torch.zeros((S, 1, cap), dtype=dtype, device=dev)
         status4 = torch.zeros((4,), dtype=torch.float64, device=dev)
         tmp = prob.new()
         rtrue = prob.new()
@@ -677,12 +637,12 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
 
         def true_residual(kd):
             """x = Q y with R y = g (the reference's lstsq solution, :403-410), r = B - A x (:414): partials -> Ptrue"""
-            call("xk_gmres_solve", dtype, ptr(st.R), ptr(st.g), ptr(ycoef), ycoef.stride(0), S, kd, st.cap)
+            call("xk_gmres_solve", dtype, ptr(st.R), ptr(st.g), ptr(st.ycoef), st.ycoef.stride(0), S, kd, st.hcap)
             x = xbufs[cur_i]
             if prob.cplx:
-                K.lincomb_c(Q, ycoef, x, kd, 1, alpha=1.0, beta=0.0, N=N)
+                K.lincomb_c(st.Q, st.ycoef, x, kd, 1, alpha=1.0, beta=0.0, N=N)
             else:
-                K.lincomb(Q, ycoef, x, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
+                K.lincomb(st.Q, st.ycoef, x, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
             if x_base is not None:
                 x.add_(x_base)
             prob.apply(x.reshape(prob.Bt, prob.nc, ld), tmp)
@@ -697,17 +657,9 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                                          "without converging (best residual %.3e); pass restart=m (GMRES(m)) or a "
                                          "max_niter <= %d" % (lazy_limit, best, lazy_limit + 1))
             nsteps = k + 1
-            if j + 2 > cap:                                           # grow the basis storage
-                newcap = min(mcyc + 1, 2 * cap)
-                Qn = torch.zeros((S, newcap, ld), dtype=dtype, device=dev)
-                Qn[:, :cap].copy_(Q)
-                Q, cap = Qn, newcap
-                ycoef = torch.zeros((S, 1, cap), dtype=dtype, device=dev)
-                st.grow(cap - 1, mcyc)
-                if prob.cplx:
-                    c1 = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
-                    c2n = torch.zeros((S, cap + 1), dtype=dtype, device=dev)
-                    gscr = torch.zeros((S * gtiles * (cap + 1) * 2,), dtype=torch.float64, device=dev)
+            if j + 2 > st.cap:
+                st.grow(min(mcyc + 1, 2 * st.cap))
+            Q = st.Q
             # w = A q_j (solve.py:390) straight into basis row j+1; with a shift E the fused shift kernel wants
             # contiguous (S, ld) arrays, so q_j / w pass through two contiguous buffers (O(N) copies)
             if prob.E is None:
@@ -718,14 +670,15 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                 Q[:, j + 1].copy_(tmp.reshape(S, ld))
             wrow = Q[:, j + 1:j + 2]
             if prob.cplx:
-                K.gmres_gram_c(Q, Q[:, j + 1], c1, gscr, j + 1, N)                 # c1[s, i] = <q_i, w>, i <= j
+                c1, c2n = st.c1, st.c2n
+                K.gmres_gram_c(Q, Q[:, j + 1], c1, st.gscr, j + 1, N)              # c1[s, i] = <q_i, w>, i <= j
                 K.lincomb_c(Q, c1.unsqueeze(1), wrow, j + 1, 1, alpha=-1.0, beta=1.0, N=N)
-                K.gmres_gram_c(Q, Q[:, j + 1], c2n, gscr, j + 1, N)                # second pass; entry j+1 = |w1|^2
+                K.gmres_gram_c(Q, Q[:, j + 1], c2n, st.gscr, j + 1, N)             # second pass; entry j+1 = |w1|^2
             else:
                 c1 = K.dense_mm(Q[:, :j + 1, :N], wrow[:, :, :N])                  # (S, 1, j+1): <q_i, w>
                 K.lincomb(Q, c1, wrow, j + 1, 1, coef_layout="ca", alpha=-1.0, beta=1.0)
                 c2n = K.dense_mm(Q[:, :j + 2, :N], wrow[:, :, :N])                 # second pass; last entry |w1|^2
-            call("xk_gmres_step", dtype, ptr(c1), c1.stride(0), ptr(c2n), c2n.stride(0), j, st.cap, ptr(st.R),
+            call("xk_gmres_step", dtype, ptr(c1), c1.stride(0), ptr(c2n), c2n.stride(0), j, st.hcap, ptr(st.R),
                  ptr(st.cs), ptr(st.sn), ptr(st.g), ptr(inv_hn), ptr(Pest), S)
             call("xk_gmres_finish", dtype, ptr(Q), ptr(c2n), c2n.stride(0), ptr(inv_hn), S, N, j, Q.stride(1),
                  Q.stride(0))
@@ -760,20 +713,15 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
                 x_base.copy_(xbufs[just])
                 rcur = rtrue.reshape(S, ld)
                 beta = rcur.norm(dim=-1)
-                Q[:, 0] = rcur / torch.where(beta == 0, torch.full_like(beta, eps), beta).unsqueeze(-1)
+                st.Q[:, 0] = rcur / torch.where(beta == 0, torch.full_like(beta, eps), beta).unsqueeze(-1)
                 for t in (st.R, st.cs, st.sn, st.g):
                     t.zero_()
                 st.g[:, 0] = beta.double()
                 cyc0 = k + 1
                 ncycles += 1
-    if trace is not None:
-        # niter counts like the reference's loop: the pass that tests x_k is pass k + 1
-        trace.update(niter=nsteps + 1, napply=prob.napply, converged=converged, best_resid=best, arnoldi_steps=nsteps,
-                     host_syncs=nsync, restarts=ncycles)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (max_niter, best)))
-    return prob.solution(xbufs[best_i].reshape(prob.Bt, prob.nc, ld))
+    # niter counts like the reference's loop: the pass that tests x_k is pass k + 1
+    return run.finish(xbufs[best_i].reshape(prob.Bt, prob.nc, ld), converged, best, nsteps + 1, max_niter,
+                      arnoldi_steps=nsteps, host_syncs=nsync, restarts=ncycles)
 
 
 # ------------------------------------------------------------------------------- MINRES
@@ -817,23 +765,15 @@ def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1
     ``A`` and ``M`` must be Hermitian and ``E`` real (``RuntimeError`` otherwise: use ``bicgstab`` or ``gmres``);
     ``posdef`` is accepted and ignored.
     """
-    from xitorch_amd.linalg import host_krylov
-    if _in_host_memory(A):
-        return host_krylov.minres(A, B, E, M, precond=precond, max_niter=max_niter, rtol=rtol, atol=atol,
-                                  max_restart=max_restart, verbose=verbose, process_group=process_group, trace=trace)
-    E = host_krylov.check_minres_inputs(A, M, E)
-    if max_niter is None:
-        max_niter = int(1.5 * A.shape[-1])
-    bdims = get_batchdims(A, B, E, M)
-    # (sharded runs: every rank takes this shortcut or none does — the loop below contains collectives)
-    if all_ranks_agree_true(torch.allclose(B, B * 0, rtol=rtol, atol=atol), B.device, process_group):
-        return _zeros_like_solution(A, B, bdims)
-    prob = _Problem(A, B, E, M, bdims, True, need_hermit=True)       # Hermitian: never the normal equations
-    if trace is not None and trace.get("k1_events") is not None:
-        prob.opA.events = trace["k1_events"]          # measurement: HIP events around every operator apply
-    kr = _Kry(prob)
+    if not _in_host_memory(A):                                       # (the host driver checks its own)
+        E = host_krylov.check_minres_inputs(A, M, E)
+    run = _Run("minres", A, B, E, M, dict(
+        precond=precond, max_niter=max_niter, rtol=rtol, atol=atol, max_restart=max_restart, verbose=verbose,
+        process_group=process_group, trace=trace), True, True)            # Hermitian: never the normal equations
+    if run.X is not None:
+        return run.X
+    prob, kr, stop, max_niter = run.prob, run.kr, run.stop, run.max_niter
     pre = _precond(precond, prob)
-    stop = _stop_vector(prob, rtol, atol)
     S, N, ld, nblk = prob.S, prob.N, prob.ld, kr.nblk
 
     x, v, Av, tmp, rtrue = (prob.new() for _ in range(5))
@@ -909,20 +849,13 @@ def minres(A, B, E=None, M=None, precond=None, max_niter=None, rtol=1e-6, atol=1
         r2.copy_(rtrue)
         w1.zero_()
         w2.zero_()
-    if trace is not None:
-        trace.update(niter=k, napply=prob.napply, converged=converged, best_resid=best, nrestart=nrestart,
-                     resid_history=hist)
-    if not converged:
-        warnings.warn(ConvergenceWarning("Convergence is not achieved after %d iterations. "
-                                         "Max norm of resid: %.3e" % (k, best)))
-    return prob.solution(x)
+    return run.finish(x, converged, best, k, k, nrestart=nrestart, resid_history=hist)
 
 
 def scipy_gmres(A, B, E=None, M=None, min_eps=1e-9, max_niter=None, **unused):
     """The reference's `method="scipy_gmres"` (wrap_gmres, solve.py:14-66): SciPy's GMRES on the host, one system at a
     time, with the operator applied wherever it lives (the reference copies every iterate between the host and the
     operator's device as well)."""
-    from xitorch_amd.linalg import host_krylov
     return host_krylov.scipy_gmres(A, B, E, M, min_eps=min_eps, max_niter=max_niter)
 
 

@@ -8,7 +8,7 @@ length m and the v side of length n.  One step:
   apply A^H on uh   -> xk_lsmr_bidiag (v half): vh <- A^H uh / beta' - (beta' / alpha) vh, partials of |vh|^2
   xk_lsmr_update: the rotations, hbar, x, h in one pass, the estimates and the per-system stop code
 
-The applies are those of `_RectOperator` (dense, CSR, banded natively; the operator's own .mm / .rmm otherwise).  The
+The applies are those of `RectPanelOperator` (dense, CSR, banded natively; the operator's own .mm / .rmm otherwise).  The
 host reads ONE word (the number of running systems, xk_kry_status on the kernels' run flags) every `resid_calc_every`
 steps and nothing else.  When no system runs (or max_niter is reached) the returned iterate is confirmed by one true
 evaluation of b - A x and A^H (b - A x) - damp^2 x (xk_kry_resid on the applies); members that stopped on S1 or S2 but
@@ -21,10 +21,9 @@ Not built: preconditioning, warm start, batch sharding, a dense `exact` method, 
 import warnings
 import torch
 from xitorch_amd import kernels as K
-from xitorch_amd._capi import NativeLibraryError, fn, ptr, call
 from xitorch_amd._util import ConvergenceWarning, bcast_shape
-from xitorch_amd.linalg._panel import pad_len, to_panel, from_panel
-from xitorch_amd.linalg.native_gkl import _RectOperator
+from xitorch_amd.linalg._panel import RectPanelOperator, pad_len, batch_count, require_hip, to_panel, from_panel
+from xitorch_amd.linalg.native_krylov import _Kry
 from xitorch_amd.linalg import host_lsmr
 
 __all__ = ["lsmr"]
@@ -61,27 +60,21 @@ class _Stacked:
 
 
 class _Side:
-    """buffers of one vector length: geometry, a zero panel, partial arrays"""
+    """buffers of one vector length: geometry, the shared Krylov kernels on it (`kr`), panels and partial arrays"""
 
-    def __init__(self, N, Bt, nc, dtype, rdtype, device):
-        vn = {torch.float64: 2, torch.float32: 4, torch.complex128: 1, torch.complex64: 2}[dtype]
+    def __init__(self, N, Bt, nc, dtype, device):
         self.N, self.ld = N, pad_len(N)
-        self.nblk = max(1, min(fn("xk_kry_max_partials")(), (N + 256 * vn * 4 - 1) // (256 * vn * 4)))
         self.shape = (Bt, nc, self.ld)
-        self.dtype, self.rdtype, self.device, self.S = dtype, rdtype, device, Bt * nc
-        self.zero = self.new()
-        self.scr = self.new()
+        self.dtype, self.device, self.S = dtype, device, Bt * nc
+        self.kr = _Kry(self)
+        self.nblk, self.partial = self.kr.nblk, self.kr.partial_real
 
     def new(self):
         return torch.zeros(self.shape, dtype=self.dtype, device=self.device)
 
-    def partial(self):
-        return torch.zeros((self.S, 64), dtype=self.rdtype, device=self.device)
-
     def resid(self, b, y, r, Prr):
-        """r = b - y (y None: r is scratch, only the partials of |b|^2 are wanted), Prr <- block partials of |r|^2"""
-        call("xk_kry_resid", self.dtype, ptr(b), ptr(self.zero if y is None else y), ptr(self.scr if r is None else r),
-             ptr(None), ptr(Prr), ptr(None), self.S, self.N, self.ld, self.nblk)
+        """r = b - y (y None: only the partials of |b|^2 are wanted), Prr <- block partials of |r|^2"""
+        self.kr.resid(b, y, r, None, Prr, None, init=y is None)
 
     def norm(self, P):
         return P[:, :self.nblk].double().sum(-1).sqrt()
@@ -98,23 +91,17 @@ def lsmr(A, B, damp=0.0, stack=None, **options):
         if stack is None:
             return host_lsmr.lsmr(A, B, damp, **options)
         return host_lsmr.lsmr_stacked(A, B, damp, stack, **options)
-    if device.type != "cuda":
-        raise NativeLibraryError("xitorch_amd lsmr runs on a HIP device only (operator is on %s)" % device)
+    require_hip(A, "lsmr")
     dtype = A.dtype
-    if dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
-        raise NativeLibraryError("xitorch_amd lsmr supports float64/float32 and complex128/complex64 operators, got %s"
-                                 % dtype)
     mm, nn = host_lsmr.stacked_shape(A, damp, stack) if stack is not None else (A.shape[-2], A.shape[-1])
     opt = host_lsmr.check_lsmr_options(A, B, damp, options, shape=(mm, nn))
     damp = float(damp)
     bdims = list(bcast_shape(A.shape[:-2], B.shape[:-2]))
-    Bt = 1
-    for d in bdims:
-        Bt *= d
+    Bt = batch_count(bdims)
     nc = B.shape[-1]
     if torch.allclose(B, B * 0):
         return torch.zeros((*bdims, nn, nc), dtype=dtype, device=device)
-    base = _RectOperator(A, bdims, Bt)
+    base = RectPanelOperator(A, bdims, Bt)
     op, kdamp = base, damp
     if stack is not None:
         kdamp = 0.0
@@ -122,26 +109,23 @@ def lsmr(A, B, damp=0.0, stack=None, **options):
             op = _Stacked(op, damp)
         if stack == "AH":
             op = _Adj(op)
-    rdtype = {torch.complex128: torch.float64, torch.complex64: torch.float32}.get(dtype, dtype)
     S = Bt * nc
     atol, btol, conlim, max_niter, every = opt["atol"], opt["btol"], opt["conlim"], opt["max_niter"], \
         opt["resid_calc_every"]
 
-    V = _Side(nn, Bt, nc, dtype, rdtype, device)
+    V = _Side(nn, Bt, nc, dtype, device)
+    rdtype = V.kr.rdtype
     x, h, hbar, vh, opv, gbuf = (V.new() for _ in range(6))
     Pv, Px, Pg, Pxx = V.partial(), (V.partial(), V.partial()), V.partial(), V.partial()
     runp = V.partial()
     state = K.lsmr_state(S, device)
     half = torch.full((S,), 0.5, dtype=rdtype, device=device)
-    rnorm = torch.zeros((S,), dtype=rdtype, device=device)
-    status = torch.zeros((2,), dtype=torch.float64, device=device)
     tr = dict(niter=0, host_reads=0, restarts=0)
     k = [0]
 
     def running():
-        call("xk_kry_status", rdtype, ptr(runp), ptr(half), ptr(rnorm), ptr(status), S, 1)
         tr["host_reads"] += 1
-        return int(status.tolist()[1])                                # the one word the host reads
+        return int(V.kr.check_status(runp, half, nblk=1)[1])          # the one word the host reads
 
     def recurrence(rop, U, rhs, rdamp, normb=None, keep=None):
         """LSMR on min |rop dx - rhs|^2 + rdamp^2 |dx|^2, dx added to x; members of `keep` sit out (stop code KEPT)"""
@@ -174,7 +158,7 @@ def lsmr(A, B, damp=0.0, stack=None, **options):
                 break
         k[0] = kk
 
-    U0 = _Side(mm, Bt, nc, dtype, rdtype, device)
+    U0 = _Side(mm, Bt, nc, dtype, device)
     rhs0 = to_panel(B.to(dtype), bdims, Bt, mm)
     rtrue, opu0, Pr = U0.new(), U0.new(), U0.partial()
     recurrence(op, U0, rhs0, kdamp)
@@ -204,7 +188,7 @@ def lsmr(A, B, damp=0.0, stack=None, **options):
         keep = ~redo
         if kdamp > 0:
             rop = _Stacked(op, kdamp)
-            U = _Side(rop.m, Bt, nc, dtype, rdtype, device)
+            U = _Side(rop.m, Bt, nc, dtype, device)
             rhs = U.new()
             rhs[:, :, :mm].copy_(rtrue[:, :, :mm])
             torch.mul(x[:, :, :nn], -kdamp, out=rhs[:, :, mm:mm + nn])
