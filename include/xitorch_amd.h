@@ -222,7 +222,12 @@ int xk_group_status_f32(const float* rmax, const int* info, const int* flag, flo
  * Lowest (uppest=0) / uppermost (uppest=1) p eigenpairs of B symmetric k x k matrices (lower
  * triangle read, pitch ldt, batch pitch sT), eigenvalues ascending: lam (B,p), Y (B,p,k) with
  * Y[b,c,:] the c-th eigenvector.  Replaces torch.linalg.eigh + _take_eigpairs
- * (symeig.py:174-175, 255-264).  k <= 128, p <= 16.  ws: xk_small_eigh_workspace_elems elements. */
+ * (symeig.py:174-175, 255-264).  k <= 128, p <= 16.  ws: xk_small_eigh_workspace_elems elements.
+ * sweeps[b]: Jacobi sweeps taken (== max_sweeps: not converged); there is no other failure flag.
+ * Scale-safe: each matrix is scaled inside the kernel by the exact power of two that brings max|T| to
+ * [1, 2) and lam is scaled back, so any finite T whose entries are representable gives the same relative
+ * accuracy (and in-range T the same bits as without the scaling); a zero matrix returns lam = 0 with unit
+ * vectors; the result for a matrix that holds a NaN or an infinity is undefined. */
 long xk_small_eigh_workspace_elems(int B, int k, int max_sweeps);
 int xk_small_eigh_f64(const double* T, double* lam, double* Y, double* ws, long ws_elems, int* sweeps,
                       int B, int k, int p, int uppest, int max_sweeps, long ldt, long sT, void* stream);

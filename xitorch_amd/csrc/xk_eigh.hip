@@ -18,7 +18,8 @@
 //     `_take_eigpairs` (symeig.py:255-264).
 //
 // Accuracy: Jacobi is backward stable with small relative errors; convergence test
-// off(T)^2 <= (eps*k)^2 * ||T||_F^2 or a sweep without rotations.
+// off(T)^2 <= (eps*k)^2 * ||T||_F^2 or a sweep without rotations.  The matrix is first scaled by the exact power of
+// two that brings max|T| to [1, 2) (and lam scaled back), so that those squares stay in range at any scale of T.
 #include "xk_common.h"
 #include "xk_lane.h"
 
@@ -35,6 +36,20 @@ __device__ __forceinline__ T block_sum_1024(T v, T* red) {
   T s = T(0);
   const int nw = blockDim.x >> 6;
   for (int i = 0; i < nw; ++i) s += red[i];
+  return s;
+}
+
+// max over the block of non-negative values (a NaN is dropped); every thread gets the same result
+template <typename T>
+__device__ __forceinline__ T block_max_1024(T v, T* red) {
+  v = wave_max(v);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  T s = T(0);
+  const int nw = blockDim.x >> 6;
+  for (int i = 0; i < nw; ++i) s = red[i] > s ? red[i] : s;
   return s;
 }
 
@@ -78,6 +93,28 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(
     S[i * ld + j] = v;
   }
   __syncthreads();
+  // ---- scale safety --------------------------------------------------------------------------
+  // Everything below compares SQUARES of entries (||T||_F^2, off(T)^2, apq^2 against |app aqq|): at 2^-100 in fp32 or
+  // 2^-520 in fp64 they are all 0, at 2^+100 / 2^+520 all inf, and the sweep loop would leave at once with the
+  // diagonal of T as "eigenvalues".  So the matrix is brought to max|S| in [1, 2) by the exact power of two, and lam
+  // is multiplied back on output: no rounding changes, in-range inputs give the bits they always gave.  A zero matrix
+  // or a non-finite maximum is left as it is.
+  T amax = T(0);
+  for (int idx = tid; idx < k2 * k2; idx += nt) {
+    const int i = idx / k2, j = idx - i * k2;
+    const T v = fabs(S[i * ld + j]);
+    amax = v > amax ? v : amax;
+  }
+  amax = block_max_1024(amax, red);
+  int sexp = 0;
+  if (amax > T(0) && amax < T(INFINITY)) sexp = ilogb(amax);
+  if (sexp != 0) {
+    for (int idx = tid; idx < k2 * k2; idx += nt) {
+      const int i = idx / k2, j = idx - i * k2;
+      S[i * ld + j] = ldexp(S[i * ld + j], -sexp);
+    }
+    __syncthreads();
+  }
   T nrm = T(0);
   for (int idx = tid; idx < k2 * k2; idx += nt) {
     const int i = idx / k2, j = idx - i * k2;
@@ -212,7 +249,7 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(
     const int pos = uppest ? rank - (k - p) : rank;
     if (pos >= 0 && pos < p) {
       sel[pos] = tid;
-      lam_out[(long)b * p + pos] = di;
+      lam_out[(long)b * p + pos] = ldexp(di, sexp);
     }
   }
   __syncthreads();

@@ -377,19 +377,27 @@ def small_eigh_big(T, k, p, uppest=False, wg=None, threads=None, algo=None):
     return lam, Y, info
 
 
-def small_eigh(T, k, p, uppest=False, max_sweeps=16, method="jacobi", threads=0, profile=None):
+def small_eigh(T, k, p, uppest=False, max_sweeps=16, method="jacobi", threads=0, profile=None, out=None):
     """Lowest / uppermost `p` eigenpairs of the symmetric (B, k, k) matrices T[:, :k, :k] (lower
     triangle is read).  Returns lam (B, p) ascending, Y (B, p, k) with Y[b, c] the c-th eigenvector, and an int32
     (B,) tensor: Jacobi sweeps (method "jacobi") or the failure flags of the self-check (method "tri": K3t,
     Householder tridiagonalisation + bisection + inverse iteration; nonzero -> redo that call with "jacobi").
+    `out`: contiguous (lam, Y, aux) of those shapes to write into instead of fresh tensors.
     Native replacement of `torch.linalg.eigh` + `_take_eigpairs` (symeig.py:174-175)."""
     require_device(T, "projected matrix")
     B = T.shape[0]
     if T.stride(2) != 1:
         raise _capi.NativeLibraryError("T must have unit stride along its last dim")
-    lam = torch.empty((B, p), dtype=T.dtype, device=T.device)
-    Y = torch.empty((B, p, k), dtype=T.dtype, device=T.device)
-    aux = torch.empty((B,), dtype=torch.int32, device=T.device)
+    if out is None:
+        lam = torch.empty((B, p), dtype=T.dtype, device=T.device)
+        Y = torch.empty((B, p, k), dtype=T.dtype, device=T.device)
+        aux = torch.empty((B,), dtype=torch.int32, device=T.device)
+    else:
+        lam, Y, aux = out
+        for t, shape, dtype in ((lam, (B, p), T.dtype), (Y, (B, p, k), T.dtype), (aux, (B,), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != T.device or not t.is_contiguous():
+                raise _capi.NativeLibraryError("small_eigh: out tensor is %s %s on %s, expected contiguous %s %s on %s"
+                                               % (tuple(t.shape), t.dtype, t.device, shape, dtype, T.device))
     if method == "tri":
         call("xk_small_eigh_tri", T.dtype, ptr(T), ptr(lam), ptr(Y), ptr(aux), B, k, p, 1 if uppest else 0, T.stride(1),
              T.stride(0), int(threads), ptr(profile))
