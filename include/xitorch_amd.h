@@ -639,6 +639,39 @@ int xk_cheb_step_c64(const float* AY, long ldA, long sA, const float* Y, long ld
                      long ldP, long sP, float* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
                      void* stream);
 
+/* ---- LOBPCG: the in-place rotation of the three panel stacks (extension: symeig method "lobpcg"; new symbols only) --
+ * S, AS and (may be NULL) MS are (Bt, rows, ld*) stacks [X | P | W] of the driver: every row a contiguous run of N
+ * elements, pitch ld* >= N, stack stride s* (elements; complex elements for _c128 / _c64, interleaved storage).
+ * C: coefficients in the panels' dtype, C[b,a,c] at C[b * sC + a * sCa + c * sCc], plain (NOT conjugated: the caller
+ * passes eigenvector columns).  lam: DOUBLES on the device, lam[b * sLam + c], c < w, read by the kernel and rounded
+ * once by the 32-bit forms.  For every b < Bt and n < N, with w <= q <= k <= xk_lobpcg_max_rows():
+ *     stack[b,c,n] <- sum_{a<k} C[b,a,c] * stack[b,a,n],   c < q,   for stack = S, MS, AS         (in place)
+ *     S[b,q+c,n]   <- AS'[b,c,n] - lam[b,c] * (MS ? MS' : S')[b,c,n],   c < w                    (the residual)
+ *     Pnorm[(b * w + c) * nblk + blk] <- sum over column chunk blk of |S[b,q+c,n]|^2   (doubles, fixed order)
+ *     Pmax[b * nblk + blk] <- max over chunk blk and c < w of |S[b,q+c,n]| (complex: the modulus; NaN is kept)
+ * nblk = xk_lobpcg_blocks(N, element bytes): chunks of 256 16 B vectors; it depends on N and the dtype only.
+ * Rows [q, q+w) of AS and MS, every row >= q + w and everything at n >= N are left alone; rows >= k are not read.
+ * Sums accumulate in the panels' real type in the order a = 0, 1, ...; no atomics, a repeat call gives the same bits.
+ * A workgroup owns its columns outright and loads all k rows of them before it stores: there is no second copy.
+ * XK_ERR_ARG, nothing launched: NULL S / AS / C / lam / Pnorm / Pmax; Bt, N or w <= 0; q < w, q > k, k above
+ * xk_lobpcg_max_rows(); a pitch below N; a stack stride below (q + w) * pitch.
+ * Every base 16 B aligned and every pitch / stack stride a multiple of the 16 B vector: vector form; any other layout:
+ * scalar form, same result contract. */
+int xk_lobpcg_max_rows(void);
+int xk_lobpcg_blocks(int N, int elem_bytes);
+int xk_lobpcg_rotate_f64(double* S, long ldS, long sS, double* AS, long ldA, long sA, double* MS, long ldM, long sM,
+                         const double* C, long sC, long sCa, long sCc, const double* lam, long sLam, double* Pnorm,
+                         double* Pmax, int Bt, int N, int k, int q, int w, void* stream);
+int xk_lobpcg_rotate_f32(float* S, long ldS, long sS, float* AS, long ldA, long sA, float* MS, long ldM, long sM,
+                         const float* C, long sC, long sCa, long sCc, const double* lam, long sLam, double* Pnorm,
+                         double* Pmax, int Bt, int N, int k, int q, int w, void* stream);
+int xk_lobpcg_rotate_c128(double* S, long ldS, long sS, double* AS, long ldA, long sA, double* MS, long ldM, long sM,
+                          const double* C, long sC, long sCa, long sCc, const double* lam, long sLam, double* Pnorm,
+                          double* Pmax, int Bt, int N, int k, int q, int w, void* stream);
+int xk_lobpcg_rotate_c64(float* S, long ldS, long sS, float* AS, long ldA, long sA, float* MS, long ldM, long sM,
+                         const float* C, long sC, long sCa, long sCc, const double* lam, long sLam, double* Pnorm,
+                         double* Pmax, int Bt, int N, int k, int q, int w, void* stream);
+
 /* ---- Golub-Kahan-Lanczos bidiagonalisation with thick restart (extension: svd method "gkl"; new symbols only, ABI stays 2) -
  * xk_gkl_sweep: one Gram-Schmidt pass of one new vector per member against j <= xk_gkl_max_rows() rows of a basis
  *   panel Q (Bt, cap, ldQ), rows are vectors (elements; complex elements for _c128 / _c64, interleaved storage):

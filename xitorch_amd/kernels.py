@@ -705,6 +705,60 @@ def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
     return rc if raw else out
 
 
+# --------------------------------------------------------------------------- LOBPCG rotation (xk_lobpcg.hip)
+def lobpcg_max_rows():
+    """largest order k of the Rayleigh-Ritz problem `lobpcg_rotate` accepts"""
+    return int(fn("xk_lobpcg_max_rows")())
+
+
+def lobpcg_blocks(N, dtype):
+    """column chunks of `lobpcg_rotate` = length of the partial-sum axis of Pnorm / Pmax"""
+    return int(fn("xk_lobpcg_blocks")(int(N), torch.empty((), dtype=dtype).element_size()))
+
+
+def lobpcg_rotate(S, AS, MS, C, lam, k, q, w, N=None, Pnorm=None, Pmax=None, raw=False):
+    """The in-place rotation of LOBPCG's stacks (xk_lobpcg_rotate_*).  S, AS, MS (None: no overlap operator):
+    (Bt, rows >= q + w, ld) stacks of one dtype, unit stride along the vector.  For c < q every stack's row c becomes
+    sum_{a<k} C[b,a,c] * row a (C (Bt, k, q) in the stacks' dtype, any strides, plain — not conjugated), and rows
+    [q, q+w) of S receive the residual AS'_c - lam[b,c] * (MS'_c or S'_c).  lam: (Bt, >= w) float64 on the device, unit
+    stride along c.  Returns (Pnorm (Bt, w, nblk), Pmax (Bt, nblk)) float64: the partial sums of |residual|^2 per column
+    and the largest |residual| entry, per column chunk (nblk = lobpcg_blocks(N, dtype)).  N: vector length (default: the
+    stacks' whole last dimension); nothing at n >= N is written.  raw=True returns the status code instead of raising
+    (tests of the argument checks) and checks nothing itself."""
+    stacks = (S, AS) if MS is None else (S, AS, MS)
+    for t in stacks:
+        require_device(t, "stack")
+    if not raw:
+        for t in stacks:
+            if t.dim() != 3 or t.dtype != S.dtype or t.shape[0] != S.shape[0] or (t.shape[2] > 1 and t.stride(2) != 1):
+                raise _capi.NativeLibraryError("lobpcg_rotate: stacks must be (Bt, rows, ld) of one dtype, unit stride "
+                                               "along the vector")
+            if t.shape[1] < q + w or t.shape[1] < k:
+                raise _capi.NativeLibraryError("lobpcg_rotate: a stack has %d rows, k = %d and q + w = %d are needed"
+                                               % (t.shape[1], k, q + w))
+        if C.dtype != S.dtype or C.dim() != 3 or C.shape[0] != S.shape[0] or C.shape[1] < k or C.shape[2] < q:
+            raise _capi.NativeLibraryError("lobpcg_rotate: C must be (Bt, >= k, >= q) in the stacks' dtype")
+        if lam.dtype != torch.float64 or lam.dim() != 2 or lam.shape[1] < w or (lam.shape[1] > 1 and lam.stride(1) != 1):
+            raise _capi.NativeLibraryError("lobpcg_rotate: lam must be (Bt, >= w) float64, unit stride along its last dim")
+    _require_resolved("lobpcg_rotate", S, AS, MS, C)
+    require_device(C, "coefficients")
+    require_device(lam, "Ritz values")
+    Bt = S.shape[0]
+    if N is None:
+        N = min(t.shape[2] for t in stacks)
+    nblk = max(1, lobpcg_blocks(max(int(N), 1), S.dtype))
+    if Pnorm is None:
+        Pnorm = torch.empty((Bt, max(int(w), 1), nblk), dtype=torch.float64, device=S.device)
+    if Pmax is None:
+        Pmax = torch.empty((Bt, nblk), dtype=torch.float64, device=S.device)
+    args = []
+    for t in (S, AS, MS):
+        args += [ptr(t), 0, 0] if t is None else [ptr(t), t.stride(1), t.stride(0)]
+    rc = call("xk_lobpcg_rotate", S.dtype, *args, ptr(C), C.stride(0), C.stride(1), C.stride(2), ptr(lam),
+              lam.stride(0), ptr(Pnorm), ptr(Pmax), Bt, int(N), int(k), int(q), int(w), raw=raw)
+    return rc if raw else (Pnorm, Pmax)
+
+
 # --------------------------------------------------------------------------- complex operators (real embedding)
 def _as_real_matrix(A):
     """zero-copy real view (.., M, 2N) of a complex matrix (.., M, N): row i = (Re A_i0, Im A_i0, Re A_i1, ...)"""

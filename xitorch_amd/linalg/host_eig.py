@@ -15,9 +15,10 @@ from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
 from xitorch_amd.dist import allreduce_max_
 
-__all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard", "gkl", "gkl_default_ncv"]
+__all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard", "gkl", "gkl_default_ncv", "lobpcg",
+           "lobpcg_default_nguard"]
 
-calls = {"davidson": 0, "chebfsi": 0, "gkl": 0}
+calls = {"davidson": 0, "chebfsi": 0, "gkl": 0, "lobpcg": 0}
 
 
 def _H(x):
@@ -534,3 +535,299 @@ def gkl(A, k, mode, max_niter=100, min_eps=1e-6, ncv=None, V0=None, v_init="rand
         trace.update(niter=niter, restarts=niter - 1, napply=napply, ncv=ncv, keep=keep, resid_history=history,
                      converged_history=conv_history, breakdowns=breakdowns, host_reads=None, panel_kernel="host", tall=tall, converged=done)
     return uu.reshape(*bdims, m, k), ss.reshape(*bdims, k), vv.reshape(*bdims, n, k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LOBPCG in its basis-orthonormal form (extension; Knyazev, SIAM J. Sci. Comput. 23 (2001) 517; Duersch, Shao, Yang, Gu,
+# SIAM J. Sci. Comput. 40 (2018) C655): symeig(method="lobpcg")
+# ---------------------------------------------------------------------------------------------------------------------
+LOBPCG_MAX_ROWS = 96         # order 3 w of the Rayleigh-Ritz problem the rotation kernel serves (xk_lobpcg_max_rows)
+
+
+def lobpcg_default_nguard(neig, N):
+    """guard vectors of the LOBPCG block: max(2, ceil(neig / 4)), capped so that neig + nguard <= N"""
+    return max(0, min(max(2, -(-neig // 4)), N - neig))
+
+
+def _lob_setup(A, neig, M, nguard, V0, process_group):
+    """argument checks and sizes shared by the host twin and the device driver: (N, bdims, B, w, hand_over)"""
+    if process_group is not None:
+        raise NotImplementedError("lobpcg: batch sharding over a process group is not supported; use method='davidson'")
+    N = A.shape[-1]
+    bdims = list(A.shape[:-2]) if M is None else list(bcast_shape(A.shape[:-2], M.shape[:-2]))
+    B = 1
+    for d in bdims:
+        B *= d
+    if nguard is None:
+        nguard = lobpcg_default_nguard(neig, N)
+    w = min(N, neig + int(nguard))
+    if V0 is not None and w < V0.shape[-1]:
+        w = min(N, V0.shape[-1])
+    hand_over = N <= max(5 * w, 16)
+    if not hand_over and 3 * w > LOBPCG_MAX_ROWS:
+        raise NotImplementedError("lobpcg: a block of %d vectors needs a Rayleigh-Ritz problem of order %d, beyond the "
+                                  "%d rows of the rotation kernel; use method='chebfsi' (many pairs, M=None) or "
+                                  "method='davidson'" % (w, 3 * w, LOBPCG_MAX_ROWS))
+    return N, bdims, B, w, hand_over
+
+
+def _lob_check_precond(precond):
+    """the strings LOBPCG takes: "diag" / "jacobi", both T = |diag A|^-1.  davidson's third spelling "davidson" names
+    its shifted form (diag A - lam diag M)^-1, which LOBPCG does not use: refused rather than reinterpreted"""
+    if isinstance(precond, str) and precond.lower() not in ("diag", "jacobi"):
+        raise RuntimeError("Unknown lobpcg preconditioner: %s (\"diag\" / \"jacobi\", a diagonal tensor or a "
+                           "LinearOperator)" % precond)
+
+
+def _lob_random(bdims, B, N, w, dtype, dev, rng_device, draw):
+    """(B, w, N) panel-major random block number `draw` of a run, from a generator of its own (the global ones are left
+    alone): the replacement of residual columns without a direction, and the redrawn W"""
+    rdev = torch.device("cpu") if rng_device == "cpu" else dev
+    g = torch.Generator(device=rdev).manual_seed(12421 + 2 + draw)
+    return torch.randn((B, w, N), dtype=dtype, device=rdev, generator=g).to(dev)
+
+
+def lob_dependent_columns(G, rdtype):
+    """(B, w) bool, on the host: the columns of a block whose Gram matrix G = X^H M X (B, w, w) a Cholesky
+    factorisation without pivoting finds dependent on the columns before them (pivot <= sqrt(u) G_jj, or not finite).
+    Runs only after a failed orthonormalisation of the START block."""
+    Gh = G.detach().cpu().to(torch.complex128 if G.is_complex() else torch.float64)
+    B, w = Gh.shape[0], Gh.shape[-1]
+    tol = float(torch.finfo(rdtype).eps) ** 0.5
+    bad = torch.zeros((B, w), dtype=torch.bool)
+    for b in range(B):
+        L = torch.zeros_like(Gh[b])
+        for j in range(w):
+            gjj = float(Gh[b, j, j].real)
+            piv = gjj - float((L[j, :j].abs() ** 2).sum())
+            if not (piv > tol * gjj) or not (gjj > 0) or piv != piv:
+                bad[b, j] = True
+                continue
+            L[j, j] = piv ** 0.5
+            if j + 1 < w:
+                L[j + 1:, j] = (Gh[b, j + 1:, j] - torch.matmul(L[j + 1:, :j], L[j, :j].conj())) / L[j, j]
+                L[j + 1:, j][bad[b, j + 1:]] = 0
+    return bad
+
+
+def lob_cp(Cx, w):
+    """The coefficient columns of the implicit search directions (Duersch et al., section 4.2): C_x (.., k, w) with
+    its X rows (the first w) zeroed, projected against C_x and orthonormalised — twice, so that columns the first QR
+    had to complete (directions that have converged away) end up orthogonal to C_x as well.  [C_x, C_p] then has
+    orthonormal columns, and with an M-orthonormal S so have X' = S C_x and P' = S C_p.  Torch ops on small tensors of
+    the operator's device, no host read."""
+    Cp = Cx.clone()
+    Cp[..., :w, :] = 0
+    for _ in range(2):
+        Cp = Cp - torch.matmul(Cx, torch.matmul(_H(Cx), Cp))
+        Cp, _R = torch.linalg.qr(Cp)
+    return Cp
+
+
+def _lob_host_precond(precond, A, M, bdims, N, dtype):
+    """davidson's grammar for operators in host memory: None, ("diag", d, None) with the (.., N) diagonal of A or the
+    caller's, or ("op", LinearOperator)"""
+    if precond is None:
+        return None
+    from xitorch_amd.linop import LinearOperator as _LinOp, MatrixLinearOperator
+
+    def diag_of(op):
+        if isinstance(op, MatrixLinearOperator):
+            return op.mat.diagonal(dim1=-2, dim2=-1)
+        return op.fullmatrix().diagonal(dim1=-2, dim2=-1)
+
+    _lob_check_precond(precond)
+    if isinstance(precond, str):
+        return ("diag", diag_of(A).expand(*bdims, N), None)
+    if isinstance(precond, torch.Tensor):
+        if precond.shape[-1] != N:
+            raise RuntimeError("precond diagonal must have shape (*batch, %d), got %s" % (N, tuple(precond.shape)))
+        return ("diag", precond.to(dtype).expand(*bdims, N), None)
+    if isinstance(precond, _LinOp):
+        return ("op", precond)
+    raise TypeError("precond must be None, 'diag', a tensor or a LinearOperator, got %s" % type(precond))
+
+
+def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, precond=None, V0=None, v_init="randn",
+           rng_device="cpu", verbose=False, trace=None, process_group=None, **unused):
+    """LOBPCG in torch ops for a Hermitian operator in HOST memory: the statement of `native_lobpcg.lobpcg` (same
+    options, same refusals, same decisions; see there).  Three blocks S = [X | P | W] of w = neig + nguard vectors
+    kept M-orthonormal, one operator product and one preconditioner product per iteration, a Rayleigh-Ritz problem of
+    order 3 w recomputed from the blocks, P formed from orthonormal coefficient columns (`lob_cp`)."""
+    import warnings
+    from xitorch_amd._util import ConvergenceWarning
+    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD, GUARD_MAX_REDO, _shift_rel
+    calls["lobpcg"] += 1
+    dev = torch.device(A.device)
+    if dev.type != "cpu":
+        raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "
+                                 "run on the HIP kernels" % dev)
+    N, bdims, B, w, hand_over = _lob_setup(A, neig, M, nguard, V0, process_group)
+    _lob_check_precond(precond)
+    dtype = A.dtype
+    if hand_over:
+        if trace is not None:
+            trace.update(niter=0, napply=0, w=w, handed_to="exacteig")
+        return exacteig(A, neig, mode, M)
+    sign = 1.0 if mode == "lowest" else -1.0
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    gbad = GUARD_BAD[rdt]
+    pc = _lob_host_precond(precond, A, M, bdims, N, dtype)
+    napply, ndraw, redraws, restarts = 0, 0, 0, 0
+    eye = torch.eye(w, dtype=dtype)
+
+    def apply(X):
+        nonlocal napply
+        napply += 1
+        return A.mm(X)
+
+    def Mmm(X):
+        return M.mm(X) if M is not None else X
+
+    def random_block():
+        nonlocal ndraw
+        ndraw += 1
+        return _lob_random(bdims, B, N, w, dtype, dev, rng_device, ndraw).transpose(-2, -1).reshape(*bdims, N, w)
+
+    def orth(W, Q, MQ, passes):
+        """W M-orthonormal and M-orthogonal to Q: `passes` x [projection, CholeskyQR], the first CholeskyQR shifted;
+        M is applied once and M W transformed alongside.  Returns (W, M W, largest Cholesky flag)."""
+        MW = Mmm(W)
+        flag = 0
+        for r in range(passes):
+            if Q is not None:
+                c = torch.matmul(_H(MQ), W)
+                W = W - torch.matmul(Q, c)
+                MW = MW - torch.matmul(MQ, c) if M is not None else W
+            G = torch.matmul(_H(W), MW)
+            G = (G + _H(G)) * 0.5
+            if r == 0 and passes > 1:
+                tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1).real
+                G = G + (_shift_rel(N, w, rdt) * tr)[..., None, None] * eye
+            L, info = torch.linalg.cholesky_ex(G)
+            flag = max(flag, int(info.max()))
+            ok = (info == 0)[..., None, None]
+            L = torch.where(ok, L, eye.expand_as(L))
+            W = torch.linalg.solve_triangular(_H(L), W, upper=True, left=False)
+            MW = torch.linalg.solve_triangular(_H(L), MW, upper=True, left=False) if M is not None else W
+        return W, MW, flag
+
+    def ritz_on_x(X, AX, MX):
+        """Rayleigh-Ritz on span(X) alone: (X, AX, MX rotated, lam (.., w), residual block)"""
+        T = torch.matmul(_H(X), AX)
+        mu, Y = torch.linalg.eigh((T + _H(T)) * (0.5 * sign))
+        lam = mu * sign
+        X, AX = torch.matmul(X, Y), torch.matmul(AX, Y)
+        MX = torch.matmul(MX, Y) if M is not None else X
+        return X, AX, MX, lam, AX - MX * lam.unsqueeze(-2).to(dtype)
+
+    def guard_of(X, MX):
+        g = float((torch.matmul(_H(X), MX) - eye).abs().max())
+        return g if g == g else float("inf")
+
+    # ---- start: M-orthonormal block, Rayleigh-Ritz on it alone
+    spare = random_block()          # random directions, drawn once: what replaces a column without a direction
+    X = _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device)          # (B, w, N)
+    X = X.transpose(-2, -1).reshape(*bdims, N, w)
+    X1, MX, flag = orth(X, None, None, 2)
+    if flag != 0 or guard_of(X1, MX) > gbad:
+        # dependent start vectors (the shifted first pass hides them from the Cholesky flag; the guard sees them): the
+        # columns a Cholesky factorisation of the Gram matrix finds dependent are drawn afresh, and the block gets
+        # three passes; a second failure raises
+        G = torch.matmul(_H(X), Mmm(X)).reshape(B, w, w)
+        bad = lob_dependent_columns(G, rdt).reshape(*bdims, 1, w)
+        redraws += int(bad.sum())
+        X1, MX, flag = orth(torch.where(bad, spare, X), None, None, 3)
+        if flag != 0:
+            raise RuntimeError("lobpcg: the start block is rank deficient (linearly dependent start vectors)")
+    X = X1
+    AX = apply(X)
+    X, AX, MX, lam, R = ritz_on_x(X, AX, MX)
+    P = AP = MP = None
+    guard = guard_of(X, MX)
+    if guard > gbad:
+        raise RuntimeError("lobpcg: the start block is not orthonormal (max|X^H M X - I| = %.2e)" % guard)
+
+    best_resid, best = float("inf"), None
+    history = []
+    niter, nfail = 0, 0
+    while True:
+        max_resid = float(R[..., :neig].abs().max())
+        if max_resid != max_resid:
+            max_resid = float("inf")
+        history.append(max_resid)
+        if verbose:
+            print("Iter %3d (block of %d): resid: %.3e" % (niter, w, max_resid))
+        if max_resid < best_resid:
+            best_resid, best = max_resid, (lam[..., :neig], X[..., :neig])
+        if max_resid < min_eps or niter >= max_niter:
+            break
+        niter += 1
+        # W = T R, columns scaled to unit norm; a column without a direction is replaced, never divided by
+        if pc is None:
+            W = R
+        elif pc[0] == "diag":
+            # Jacobi: T = |diag|^-1, positive definite as LOBPCG needs it.  (Davidson's denominator diag A - lam diag M
+            # is indefinite for every column but the first: 142 iterations with it on the diagonally dominant test
+            # matrix, 13 with this one, 72 without a preconditioner.)
+            W = R / pc[1].abs().clamp(min=float(torch.finfo(rdt).eps) ** 0.5).unsqueeze(-1).to(dtype)
+        else:
+            W = pc[1].mm(R)
+        nrm = torch.linalg.vector_norm(W, dim=-2, keepdim=True)
+        bad = ~(torch.isfinite(nrm) & (nrm > 0))
+        if bool(bad.any()):
+            redraws += int(bad.sum())
+            W = torch.where(bad, spare, W)
+            nrm = torch.where(bad, torch.ones_like(nrm), nrm)
+        W = W / nrm
+        Q = X if P is None else torch.cat((X, P), dim=-1)
+        AQ = AX if P is None else torch.cat((AX, AP), dim=-1)
+        MQ = Q if M is None else (MX if P is None else torch.cat((MX, MP), dim=-1))
+        W1, MW, flag = orth(W, Q, MQ, 2)
+        if flag != 0:
+            redraws += w
+            W1, MW, flag = orth(random_block(), Q, MQ, 3)
+            if flag != 0:
+                raise RuntimeError("xitorch_amd lobpcg: the new directions could not be orthonormalised against the "
+                                   "block (Cholesky flag %d at iteration %d)" % (flag, niter))
+        W = W1
+        AW = apply(W)
+        S, AS = torch.cat((Q, W), dim=-1), torch.cat((AQ, AW), dim=-1)
+        MS = S if M is None else torch.cat((MQ, MW), dim=-1)
+        T = torch.matmul(_H(S), AS)                                   # recomputed from the blocks every iteration
+        mu, Y = torch.linalg.eigh((T + _H(T)) * (0.5 * sign))
+        Cx = Y[..., :w]
+        lam = mu[..., :w] * sign
+        Cp = lob_cp(Cx, w)
+        X, P = torch.matmul(S, Cx), torch.matmul(S, Cp)
+        AX, AP = torch.matmul(AS, Cx), torch.matmul(AS, Cp)
+        MX, MP = (torch.matmul(MS, Cx), torch.matmul(MS, Cp)) if M is not None else (X, P)
+        R = AX - MX * lam.unsqueeze(-2).to(dtype)
+        guard = guard_of(X, MX)
+        if guard > gbad:
+            # never returned or kept: re-orthonormalise X, drop P (the next problem has order 2 w), go on
+            restarts += 1
+            nfail += 1
+            if nfail > GUARD_MAX_REDO:
+                raise RuntimeError("xitorch_amd lobpcg: the block lost its orthonormality %d times (max|X^H M X - I| = "
+                                   "%.2e at iteration %d)" % (nfail, guard, niter))
+            X, MX, flag = orth(X, None, None, 3)
+            if flag != 0:
+                raise RuntimeError("xitorch_amd lobpcg: the block is rank deficient after a guard failure")
+            AX = apply(X)
+            X, AX, MX, lam, R = ritz_on_x(X, AX, MX)
+            P = AP = MP = None
+            if guard_of(X, MX) > gbad:
+                R = torch.full_like(R, float("inf"))
+    if best is None:
+        raise RuntimeError("xitorch_amd lobpcg: no finite residual was produced")
+    if not best_resid < min_eps:
+        warnings.warn(ConvergenceWarning("lobpcg: convergence is not achieved after %d iterations (max |resid| = %.3e "
+                                         ">= min_eps = %.3e); the best block is returned" % (niter, best_resid, min_eps)))
+    if trace is not None:
+        trace.update(niter=niter, napply=napply, w=w, resid_history=history, best_resid=best_resid, restarts=restarts,
+                     redraws=redraws, small_eigh="library", panel_kernel="host")
+    evals, evecs = best
+    if mode != "lowest":
+        evals, evecs = evals.flip(-1), evecs.flip(-1)
+    return evals, evecs

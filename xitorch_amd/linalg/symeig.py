@@ -11,6 +11,7 @@ from xitorch_amd.linop import LinearOperator  # noqa: F401  (re-exported for typ
 from xitorch_amd.linalg.solve import solve
 from xitorch_amd.linalg.native_eig import davidson, exacteig
 from xitorch_amd.linalg.native_chebfsi import chebfsi
+from xitorch_amd.linalg.native_lobpcg import lobpcg
 from xitorch_amd.debug import is_debug_enabled
 from xitorch_amd._util import assert_runtime, merge_options, null_context, get_method, pop_keys, MathWarning
 
@@ -47,7 +48,10 @@ def symeig(A, neig=None, mode="lowest", M=None, bck_options={}, method=None, **f
     method: str or callable or None
         ``"exacteig"`` (default, dense), ``"davidson"`` (native HIP block Davidson), ``"chebfsi"`` (Chebyshev-filtered
         subspace iteration on the HIP kernels: a fixed block of ``neig + nguard`` vectors, for many pairs; ``M=None``; complex
-        blocks wider than 32 vectors solve their small eigenproblem with ``torch.linalg.eigh``), or a callable
+        blocks wider than 32 vectors solve their small eigenproblem with ``torch.linalg.eigh``), ``"lobpcg"`` (LOBPCG in
+        its basis-orthonormal form on the HIP kernels: constant storage of three stacks of ``3 (neig + nguard)`` vectors,
+        takes ``M`` and ``precond=`` like ``davidson``; complex blocks wider than 16 vectors solve their small
+        eigenproblem with ``torch.linalg.eigh``), or a callable
         ``f(A, neig, mode, M, **fwd_options) -> (evals, evecs)``
     **fwd_options
         Method-specific options
@@ -190,7 +194,7 @@ def _custom_exacteig(A, neig, mode, M=None, **options):
     return exacteig(A, neig, mode, M)
 
 
-_SYMEIG_METHODS = {"davidson": davidson, "chebfsi": chebfsi, "custom_exacteig": _custom_exacteig}
+_SYMEIG_METHODS = {"davidson": davidson, "chebfsi": chebfsi, "lobpcg": lobpcg, "custom_exacteig": _custom_exacteig}
 
 
 class _SymeigFunction(torch.autograd.Function):
