@@ -14,6 +14,7 @@ import torch
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
 from xitorch_amd.dist import allreduce_max_
+from xitorch_amd.linalg._block import _initial_block, _shard_of_global_batch, _shift_rel, GUARD_BAD, GUARD_MAX_REDO
 
 __all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard", "gkl", "gkl_default_ncv", "lobpcg",
            "lobpcg_default_nguard"]
@@ -62,7 +63,6 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
     if precond is not None or restart is not None:
         raise NativeLibraryError("precond= / restart= are extensions of the HIP davidson; not available for an "
                                  "operator in host memory")
-    from xitorch_amd.linalg.native_eig import _initial_block, _shard_of_global_batch
     N = A.shape[-1]
     if nguess is None:
         nguess = neig
@@ -184,7 +184,6 @@ def _cheb_lanczos_vector(bdims, N, dtype):
 def _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device):
     """(B, w, N) panel-major start block: `_initial_block`'s, a caller's V0 completed by random columns when it has
     fewer than w"""
-    from xitorch_amd.linalg.native_eig import _initial_block
     if V0 is None:
         return _initial_block(v_init, None, bdims, B, N, w, dtype, dev, rng_device)
     V = _initial_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device)
@@ -205,7 +204,7 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     pass and half the degree, which stay in force for the rest of the run; a second failure raises.  Stopping rule, best-block return and the guard thresholds are davidson's."""
     import warnings
     from xitorch_amd._util import ConvergenceWarning
-    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD
+    from xitorch_amd.linalg.native_eig import exacteig
     calls["chebfsi"] += 1
     _cheb_check_args("chebfsi", M, process_group)
     dev = torch.device(A.device)
@@ -384,7 +383,6 @@ def _gkl_dense(A, k, mode):
 def _gkl_start_vector(A, V0, v_init, bdims, B, nn, tall, dtype, dev, rng_device):
     """(B, nn) start vector on the SHORT side.  V0 (*batch, n, k0) holds guesses of right singular vectors of A: their
     sum starts the iteration (through A when the short side is the left one)."""
-    from xitorch_amd.linalg.native_eig import _initial_block
     if V0 is not None:
         if V0.shape[-2] != A.shape[-1]:
             raise RuntimeError("V0 must have shape (*batch, %d, k0), got %s" % (A.shape[-1], tuple(V0.shape)))
@@ -656,7 +654,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     order 3 w recomputed from the blocks, P formed from orthonormal coefficient columns (`lob_cp`)."""
     import warnings
     from xitorch_amd._util import ConvergenceWarning
-    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD, GUARD_MAX_REDO, _shift_rel
+    from xitorch_amd.linalg.native_eig import exacteig
     calls["lobpcg"] += 1
     dev = torch.device(A.device)
     if dev.type != "cpu":

@@ -25,6 +25,7 @@ import torch
 from xitorch_amd import kernels as K
 from xitorch_amd._util import ConvergenceWarning
 from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, real_dtype, require_hip
+from xitorch_amd.linalg._block import block_ops, native_partial_eigh, GUARD_BAD
 from xitorch_amd.linalg.native_krylov import _Kry
 from xitorch_amd.linalg import host_eig
 from xitorch_amd.linalg.host_eig import cheb_coefficients, cheb_default_nguard
@@ -32,147 +33,22 @@ from xitorch_amd.linalg.host_eig import cheb_coefficients, cheb_default_nguard
 __all__ = ["chebfsi"]
 
 
-class _RealBlock:
-    """fp64 / fp32 blocks: zero-padded (Bt, w, pad_len(N)) panels on the Davidson chain kernels"""
-
-    def __init__(self, Bt, N, w, neig, dtype, device):
-        from xitorch_amd.linalg.native_eig import EXACTEIG_NATIVE_MAX_P
-        self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
-        self.ld = pad_len(N)
-        q = max(w, 32)
-        self.C = torch.empty((Bt * q * q,), dtype=dtype, device=device)
-        self.W = torch.empty((Bt * 32 * 32,), dtype=dtype, device=device)
-        self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
-        self.rmax = torch.zeros((Bt,), dtype=dtype, device=device)
-        self.orth_g = torch.zeros((Bt,), dtype=dtype, device=device)
-        self.status = torch.zeros((5,), dtype=torch.float64, device=device)
-        self.native = (8 <= w <= EXACTEIG_NATIVE_MAX_P and K.small_eigh_big_ok(w, w, dtype)) or \
-            (w < 8 and w <= K.SMALL_EIGH_MAX_P)
-        self.small_eigh = "native" if self.native else "library"
-
-    def panel(self):
-        return torch.zeros((self.Bt, self.w, self.ld), dtype=self.dtype, device=self.device)
-
-    def load(self, P, V0p):
-        P[:, :, :self.N].copy_(V0p)
-
-    def orth(self, P, passes):
-        self.info.zero_()
-        K.davidson_orth(P, self.N, 0, self.w, self.C, self.W, self.info, passes=passes)
-
-    def rayleigh_ritz(self, Q, AQ, X, scratch, sign):
-        """X <- the Ritz block of span(Q) ordered by sign * lambda ascending; returns (lam (Bt, w) true eigenvalues in
-        that order, mu = sign * lam (ascending), [max|resid| over the wanted columns, Cholesky flag, guard])"""
-        from xitorch_amd.linalg.native_eig import native_partial_eigh
-        N, w, neig = self.N, self.w, self.neig
-        G = K.dense_mm(Q[:, :, :N], AQ[:, :, :N])                        # G[b, c, a] = <Q_a, (A Q)_c>
-        T = ((G + G.transpose(1, 2)) * (0.5 * sign)).contiguous()
-        if self.native and w >= 8:
-            mu, Y = native_partial_eigh(T, w, "lowest")                 # (Bt, w), (Bt, w, w) = [basis index, pair]
-        elif self.native:
-            mu, Yt, _ = K.small_eigh(T, w, w)                            # LDS Jacobi kernel (tiny blocks)
-            Y = Yt.transpose(1, 2)
-        else:
-            mu, Y = torch.linalg.eigh(T)                                 # beyond the native dense eigensolver's widths
-        lam = (mu * sign).contiguous()
-        self.rmax.zero_()
-        K.ritz_residual(Q, AQ, Y, lam, X, scratch, self.rmax, w, neig)
-        if w > neig:
-            K.lincomb(Q, Y[:, :, neig:], X[:, neig:], w, w - neig, coef_layout="ac", alpha=1.0, beta=0.0)
-        K.ritz_guard(X, self.orth_g, w, self.ld)
-        K.group_status(self.rmax, self.info, None, self.status, orth=self.orth_g)
-        st = self.status.tolist()                                        # the one host read of the outer iteration
-        return lam, mu, (st[0], st[1], st[4])
-
-    def result(self, X, bdims):
-        return X[:, :self.neig, :self.N].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
-
-
-class _ComplexBlock:
-    """complex128 / complex64 blocks of any width: (Bt, w, N) panels on the Hermitian Davidson kernels (xk_herm_*)"""
-
-    def __init__(self, Bt, N, w, neig, dtype, device):
-        self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
-        self.ld = N
-        self.rdtype = real_dtype(dtype)
-        self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
-        self.status = torch.zeros((Bt + 1,), dtype=torch.float64, device=device)
-        self.counts = {"rr_native": 0, "rr_library": 0}
-        # xk_herm_eigh returns up to 16 pairs from either end of the spectrum: blocks of up to 32 vectors get all their
-        # pairs from two native calls (the lowest 16 and the uppermost w - 16); wider ones go to the library
-        self.native = w <= 2 * K.HERM_EIGH_MAX_P and w <= K.HERM_EIGH_MAX_K
-        self.small_eigh = "native" if self.native else "library"
-        self.eye = torch.eye(w, dtype=dtype, device=device)
-
-    def panel(self):
-        return torch.zeros((self.Bt, self.w, self.N), dtype=self.dtype, device=self.device)
-
-    def load(self, P, V0p):
-        P.copy_(V0p)
-
-    def orth(self, P, passes):
-        """CholeskyQR of the block with `passes` passes (the first shifted when there are several).  Blocks wider than
-        the 32 vectors of xk_herm_cholqr are taken 32 rows at a time, like xk_davidson_orth takes real ones: every chunk
-        is projected against the chunks before it (K1 Gram + K1 combination) and orthonormalised among itself, at
-        least twice — block Gram-Schmidt with CholeskyQR inside the blocks."""
-        from xitorch_amd.linalg.native_eig_herm import _shift_rel, _gram, _combine
-        self.info.zero_()
-        Q = K.HERM_CHOLQR_MAX_Q
-        for off in range(0, self.w, Q):
-            qc = min(Q, self.w - off)
-            chunk = P[:, off:off + qc]
-            np_ = max(1, passes) if off == 0 else max(2, passes)
-            for r in range(np_):
-                if off > 0:
-                    chunk.sub_(_combine(P[:, :off], _gram(P[:, :off], chunk)))
-                K.herm_cholqr(chunk, self.info, shift_rel=_shift_rel(self.N, qc, self.rdtype) if (r == 0 and np_ > 1)
-                              else 0.0)
-
-    def _eigh_all(self, T):
-        """all w eigenpairs of the Hermitian (Bt, w, w) T, ascending: (mu (Bt, w), Y (Bt, w, w) = [index, pair])"""
-        from xitorch_amd.linalg.native_eig_herm import herm_partial_eigh
-        w, P16 = self.w, K.HERM_EIGH_MAX_P
-        if not self.native:
-            self.counts["rr_library"] += 1
-            return torch.linalg.eigh(T)
-        if w <= P16:
-            return herm_partial_eigh(T, w, w, "lowest", self.counts)
-        mu_lo, Y_lo = herm_partial_eigh(T, w, P16, "lowest", self.counts)
-        mu_hi, Y_hi = herm_partial_eigh(T, w, w - P16, "uppest", self.counts)
-        # The seam.  xk_herm_eigh orthogonalises its vectors only within one call: vector 16 and vector 17 come out
-        # orthogonal to about eps |T| / gap.  Where that could reach the guard's GOOD level — eigenvalues 16 and 17 of
-        # some member closer than eps |T| / GUARD_GOOD — the call is served by the library, whose vectors are orthonormal
-        # whatever the gaps (one more host read, only for blocks of 17 .. 32 vectors).  Otherwise what is left across
-        # the seam is removed by one projection of the upper set against the lower and a renormalisation, a
-        # perturbation of the upper vectors below GUARD_GOOD.
-        from xitorch_amd.linalg.native_eig import GUARD_GOOD
-        scale = torch.maximum(mu_lo[:, 0].abs(), mu_hi[:, -1].abs())
-        tol = torch.finfo(self.rdtype).eps / GUARD_GOOD[self.rdtype]
-        if bool(((mu_hi[:, 0] - mu_lo[:, -1]) <= tol * scale).any()):
-            self.counts["rr_library"] += 1
-            return torch.linalg.eigh(T)
-        Y_hi = Y_hi - torch.matmul(Y_lo, torch.matmul(Y_lo.transpose(1, 2).conj(), Y_hi))
-        Y_hi = Y_hi / torch.linalg.vector_norm(Y_hi, dim=1, keepdim=True)
-        return torch.cat((mu_lo, mu_hi), dim=-1), torch.cat((Y_lo, Y_hi), dim=-1)
-
-    def rayleigh_ritz(self, Q, AQ, X, scratch, sign):
-        from xitorch_amd.linalg.native_eig_herm import _gram, _combine
-        w, neig = self.w, self.neig
-        T = _gram(Q, AQ)                                                  # T[b, i, c] = <Q_i, (A Q)_c>
-        T = ((T + T.transpose(1, 2).conj()) * (0.5 * sign)).contiguous()
-        mu, Y = self._eigh_all(T)
-        if self.counts["rr_library"]:
-            self.small_eigh = "library"
-        lam = (mu * sign).contiguous()
-        K.herm_ritz(Q, AQ, Y, lam, X, scratch, self.status, w, neig)
-        if w > neig:
-            X[:, neig:].copy_(_combine(Q, Y[:, :, neig:].contiguous()))
-        guard = (_gram(X, X) - self.eye).abs().max().to(torch.float64)
-        st = torch.stack((self.status[0], self.info.max().to(torch.float64), guard)).tolist()
-        return lam, mu, (st[0], st[1], st[2])
-
-    def result(self, X, bdims):
-        return X[:, :self.neig].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
+def _rayleigh_ritz(ops, Q, AQ, X, scratch, hstatus, neig, sign):
+    """X <- the Ritz block of span(Q) ordered by sign * lambda ascending; returns (lam (Bt, w) true eigenvalues in
+    that order, mu = sign * lam (ascending), [max|resid| over the wanted columns, Cholesky flag, guard])"""
+    w = ops.w
+    T = ops.rr_matrix(Q, AQ, sign)                                       # T[b, i, c] = sign <Q_i, (A Q)_c>
+    mu, Y = ops.eigh_lowest(T, w, w)                                     # (Bt, w), (Bt, w, w) = [basis index, pair]
+    lam = (mu * sign).contiguous()
+    if hstatus is None:
+        ops.rmax.zero_()
+        K.ritz_residual(Q, AQ, Y, lam, X, scratch, ops.rmax, w, neig)
+    else:
+        K.herm_ritz(Q, AQ, Y, lam, X, scratch, hstatus, w, neig)
+    if w > neig:
+        ops.combine(Q, Y[:, :, neig:], out=X[:, neig:])                  # the guard columns
+    # the one host read of the outer iteration
+    return lam, mu, ops.status(X, w, None if hstatus is None else hstatus[0], ops.info)
 
 
 def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
@@ -217,7 +93,6 @@ def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
     if steps <= K.SMALL_EIGH_MAX_P:
         theta, _, _ = K.small_eigh(Tl, steps, steps)
     else:
-        from xitorch_amd.linalg.native_eig import native_partial_eigh
         theta, _ = native_partial_eigh(Tl, steps, "lowest")
     return theta, beta
 
@@ -256,7 +131,7 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     pass and half the degree, and both stay in force for the rest of the run (a block that lost its orthonormality once
     is not given the longer filter again); a second failure raises.
     """
-    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD
+    from xitorch_amd.linalg.native_eig import exacteig
     device = torch.device(A.device)
     if device.type == "cpu":
         # device dispatch (see native_eig.davidson): an operator in HOST memory is served by host_eig.py
@@ -280,17 +155,22 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
         return exacteig(A, neig, mode, None)
     sign = 1.0 if mode == "lowest" else -1.0
     rdt = real_dtype(dtype)
-    blk = (_ComplexBlock if dtype.is_complex else _RealBlock)(Bt, N, w, neig, dtype, device)
+    ops = block_ops(Bt, N, w, dtype, device, wide=True)
+    hstatus = torch.zeros((Bt + 1,), dtype=torch.float64, device=device) if dtype.is_complex else None   # xk_herm_ritz
     op = PanelOperator(A, bdims, Bt, N)
     if trace is not None and trace.get("k1_events") is not None:
         op.events = trace["k1_events"]
 
-    X, R0, R1, AY = blk.panel(), blk.panel(), blk.panel(), blk.panel()
-    best_X = blk.panel()
-    Tn = blk.panel()[:, :neig]                       # residual panel xk_ritz_residual writes beside the wanted columns
-    blk.load(X, host_eig._cheb_start_block(v_init, V0, bdims, Bt, N, w, dtype, device, rng_device))
-    blk.orth(X, 2)
-    if int(blk.info.max().item()) != 0:
+    def orth(P, passes):
+        # two passes of CholeskyQR (the first shifted); complex blocks in chunks of xk_herm_cholqr's 32 vectors
+        ops.info.zero_()
+        ops.orth(P, 0, w, passes, ops.info, chunk=K.HERM_CHOLQR_MAX_Q)
+
+    X, R0, R1, AY, best_X = (ops.panel(w) for _ in range(5))
+    Tn = ops.panel(w)[:, :neig]                      # residual panel xk_ritz_residual writes beside the wanted columns
+    ops.load(X, host_eig._cheb_start_block(v_init, V0, bdims, Bt, N, w, dtype, device, rng_device))
+    orth(X, 2)
+    if int(ops.info.max().item()) != 0:
         raise RuntimeError("chebfsi: the start block is rank deficient (linearly dependent start vectors)")
 
     ks = max(2, min(int(lanczos_steps), N - 1))
@@ -323,9 +203,9 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
                 Yp, Y = Y, out
             Q = Y
             other = R1 if Q is R0 else R0                                                # Y_{m-1} (dead) or unused
-            blk.orth(Q, passes)
+            orth(Q, passes)
             op.apply(Q, AY)
-            lam, mu, (max_resid, chol_flag, guard) = blk.rayleigh_ritz(Q, AY, other, Tn, sign)
+            lam, mu, (max_resid, chol_flag, guard) = _rayleigh_ritz(ops, Q, AY, other, Tn, hstatus, neig, sign)
             if guard != guard:
                 guard = float("inf")
             if chol_flag == 0 and guard <= gbad:
@@ -357,10 +237,10 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     if trace is not None:
         trace.update(niter=niter, napply=op.napply, degree=deg_now, w=w, resid_history=history, best_resid=best_resid,
                      bounds={"a": a.tolist(), "b_sup": b_sup.tolist(), "a0": a0.tolist()},
-                     small_eigh=blk.small_eigh, guard_redo=redo,
+                     small_eigh=ops.small_eigh, guard_redo=redo,
                      panel_kernel=op.last_kernel if op.kind != "generic" else "generic")
     evals = best_lam.reshape(*bdims, neig)
-    evecs = blk.result(best_X, bdims)
+    evecs = ops.result(best_X, neig, bdims)
     if mode != "lowest":
         evals, evecs = evals.flip(-1), evecs.flip(-1)
     return evals, evecs

@@ -32,6 +32,10 @@ from xitorch_amd import kernels as K
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
 from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, require_hip
+# (EXACTEIG_NATIVE_MAX_P is not used below: re-exported under the name the tests know, like the rest of this list)
+from xitorch_amd.linalg._block import (cholqr_step, take_eigpairs, native_partial_eigh, _native_dense_ok, _initial_block,
+                                       _shard_of_global_batch, _preconditioner, _pc_slice, K3G_MAX_K, GUARD_GOOD,
+                                       GUARD_BAD, GUARD_MAX_REDO, EXACTEIG_NATIVE_MAX_P)
 from xitorch_amd.dist import allreduce_max_
 
 __all__ = ["davidson", "exacteig", "take_eigpairs", "tallqr_extend", "native_partial_eigh"]
@@ -41,77 +45,13 @@ _PRELAUNCH = True          # enqueue the next group's chain early (module attrib
 # matrix: xk_eigh_big.hip) serves before the library takes over (>= 16 matrices per group, fewer)
 CHAIN_CUS = "all"             # units of the chain streams in the two-group pipeline: "all" | "reserved" (only the units the
                               # panel stream's mask leaves) | "auto" (measurement knob, scripts/timeline_gaps.py)
-K3G_MAX_K = [1536, 1024]      # largest basis K3g serves before the library takes over, [>= 16 matrices per group, fewer]:
-                              # measured r06 (order 1200 / 1536, ms): 1 matrix 44.5 / 83.1 native against 28.2 / 37.1 library,
-                              # 4: 45.6 / 85.1 against 34.8 / 50.5, 32: 76.2 / 150.4 against 111.8 / 198.6; at 1024: 26.6 / 24.0, 44.2 / 75.1
 K3P_MIN_K = int(os.environ.get("XITORCH_K3P_MIN_K", "80"))   # from this order on K3p + K3g's final kernel replace K3t
                               # (r06; the environment variable is a measurement knob: 129 restores K3t)
-
-
-def take_eigpairs(evals, evecs, neig, mode):
-    """First (``lowest``) or last (``uppest``) ``neig`` pairs of an ascending ``eigh`` result; the
-    returned eigenvalues are ascending in both modes (reference: symeig.py:255-264)."""
-    if mode == "lowest":
-        return evals[..., :neig], evecs[..., :neig]
-    return evals[..., -neig:], evecs[..., -neig:]
-
-
-def _shift_rel(N, q, rdtype):
-    """first-pass shift of shifted CholeskyQR (Fukaya et al.), relative to trace(G): 11 (N q + q (q + 1)) u, capped, as
-    xk_davidson_orth chooses it"""
-    u = torch.finfo(rdtype).eps * 0.5
-    return min(11.0 * (N * q + q * (q + 1)) * u, 1e-3)
 
 
 def _gram(Vrows, k, panel, p, N):
     """G[b, c, a] = <V_a, panel_c>  (B, p, k) via K1 with the basis as the 'matrix'."""
     return K.dense_mm(Vrows[:, :k, :N], panel[:, :p, :N])
-
-
-def _shard_of_global_batch(B, device, process_group):
-    """(offset, total) of this rank's B members in the group's global batch: the ranks hold consecutive blocks in rank
-    order (how `dist.shard_range` deals a batch out); one all-gather of the local counts, once per call."""
-    world = torch.distributed.get_world_size(process_group)
-    rank = torch.distributed.get_rank(process_group)
-    mine = torch.tensor([float(B)], dtype=torch.float64, device=device)
-    allb = [torch.zeros_like(mine) for _ in range(world)]
-    torch.distributed.all_gather(allb, mine, group=process_group)
-    counts = [int(round(v.item())) for v in allb]
-    return sum(counts[:rank]), sum(counts)
-
-
-def _initial_block(v_init, V0, bdims, B, N, nguess, dtype, device, rng_device="cpu", shard=None):
-    """The start block (reference: symeig.py:236-246).  `shard` = (offset, total) on a batch-sharded run: the random
-    kinds draw the block of the WHOLE batch from seed 12421 and keep this rank's members, so that member b of an
-    N-GPU run starts from the same vectors as member b of the one-GPU run (same iterates, same iteration count)."""
-    if V0 is not None:
-        if V0.shape[-2] != N:
-            raise RuntimeError("V0 must have shape (*batch, %d, nguess), got %s" % (N, tuple(V0.shape)))
-        V = V0.to(device=device, dtype=dtype).expand(*bdims, N, V0.shape[-1]).reshape(B, N, V0.shape[-1])
-        return V.transpose(-2, -1)
-    kind = v_init.lower()
-    if kind == "cos":
-        # (extension) RNG-free closed form generated on the device: V0[i,j] = cos(0.1 (i+1)(j+1) + 0.05 b)
-        from xitorch_amd import synthetic
-        return synthetic.start_block(B, N, nguess, dtype, device)
-    # seed 12421 on the global generators, like the reference (symeig.py:236-246, quirk Q5).
-    # rng_device="cpu" (default) draws from the CPU stream = the reference's CPU path (parity runs);
-    # rng_device="device" draws on the operator's device = what the reference does for a GPU operator.
-    torch.manual_seed(12421)
-    rdev = torch.device("cpu") if rng_device == "cpu" else device
-    if kind == "eye":
-        V = torch.eye(N, nguess, dtype=dtype, device=rdev).unsqueeze(0).repeat(B, 1, 1)
-    elif kind in ("randn", "rand", "random"):
-        draw = torch.randn if kind == "randn" else torch.rand
-        if shard is not None and shard[1] != B:
-            off, total = shard
-            # (the generators fill a tensor as a function of its whole size: draw the whole batch, keep the shard)
-            V = draw((total, N, nguess), dtype=dtype, device=rdev)[off:off + B].clone()
-        else:
-            V = draw((*bdims, N, nguess), dtype=dtype, device=rdev).reshape(B, N, nguess)
-    else:
-        raise ValueError("Unknown v_init type: %s" % kind)
-    return V.to(device).transpose(-2, -1)
 
 
 class _Group:
@@ -201,21 +141,12 @@ class _Group:
         if self.opM is None and self.fast and not shifted:
             K.davidson_orth(self.Vs, N, k0, q, self.scratch(q), self.Wflat, self.info, passes=0)
             return
-        panel = self.Vs[:, k0:k0 + q]
-        if self.opM is None:
-            G = K.dense_mm(panel[:, :, :N], panel[:, :, :N])
-        else:
-            self.opM.apply(panel, self.MVs[:, k0:k0 + q])
-            G = K.dense_mm(panel[:, :, :N], self.MVs[:, k0:k0 + q, :N])
-        if shifted:
-            sh = _shift_rel(N, q, self.dtype)
-            tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1)
-            G = G + (sh * tr)[:, None, None] * torch.eye(q, dtype=G.dtype, device=G.device)
-        Wq = self.Wflat[:self.B * q * q].view(self.B, q, q)      # compact (B, q, q), as the C ABI expects
-        K.panel_chol(G, Wq, self.info, q)
-        K.panel_transform(panel, Wq, q)
+        bufs = [self.Vs[:, k0:k0 + q]]
         if self.opM is not None:
-            K.panel_transform(self.MVs[:, k0:k0 + q], Wq, q)
+            bufs.append(self.MVs[:, k0:k0 + q])
+            self.opM.apply(bufs[0], bufs[1])
+        Wq = self.Wflat[:self.B * q * q].view(self.B, q, q)      # compact (B, q, q), as the C ABI expects
+        cholqr_step(bufs, bufs[-1], N, q, self.info, Wq, shift=shifted)
 
     def project_out(self, k0, q):
         """panel <- panel - V (V^H M panel) for the basis rows [0, k0)."""
@@ -435,7 +366,7 @@ class _Group:
         transformations (no operator apply), then T = V^T A V is rebuilt whole.  The basis a roll-back returns to
         passed the guard only in the directions of its Ritz block; without this step what it has lost elsewhere stays
         (measured: a residual floor of |A| times the loss, the run then grows to the full space)."""
-        N, B = self.N, self.B
+        N = self.N
         bufs = [b for b in (self.Vs, self.AVs, self.MVs) if b is not None]
         coef_basis = self.Vs if self.opM is None else self.MVs
         k0 = 0
@@ -448,16 +379,7 @@ class _Group:
                     for buf in bufs:
                         K.lincomb(buf, C, buf[:, k0:k0 + q], k0, q, coef_layout="ca", alpha=-1.0, beta=1.0)
                 Mp = panel if self.opM is None else self.MVs[:, k0:k0 + q]
-                G = K.dense_mm(panel[:, :, :N], Mp[:, :, :N])
-                G = (G + G.transpose(1, 2)) * 0.5
-                if it == 0:
-                    sh = _shift_rel(N, q, self.dtype)
-                    tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1)
-                    G = G + (sh * tr)[:, None, None] * torch.eye(q, dtype=G.dtype, device=G.device)
-                Wq = torch.empty((B, q, q), dtype=self.dtype, device=self.device)
-                K.panel_chol(G.contiguous(), Wq, self.info, q)
-                for buf in bufs:
-                    K.panel_transform(buf[:, k0:k0 + q], Wq, q)
+                cholqr_step([buf[:, k0:k0 + q] for buf in bufs], Mp, N, q, self.info, shift=(it == 0), symmetrise=True)
             k0 += q
         Tn = K.dense_mm(self.Vs[:, :k, :N], self.AVs[:, :k, :N], wide=False)   # Tn[b,c,a] = <V_a, (A V)_c>
         self.T[:, :k, :k] = (Tn + Tn.transpose(1, 2)) * 0.5
@@ -588,20 +510,6 @@ def _sub_operator(A, B, N, b0, b1):
 
 class _GuardFailure(RuntimeError):
     """the a-posteriori guard failed and the run cannot be rolled back to a basis that passed it"""
-
-
-# A-posteriori guard on every Rayleigh-Ritz block, g = max|X^T M X - I| over the batch (status[4]):
-#   g <= GOOD            the basis width of this step becomes the roll-back point
-#   GOOD < g <= BAD      the rest of the run takes two projection passes (nothing is undone)
-#   g > BAD (or NaN)     the step is void: never a best / converged iterate; the run goes back to the last roll-back
-#                        point with re-orthogonalised passes (trace["orth_redo"]); with none left it is repeated from the
-#                        start block with three passes, and if that fails too an error is raised
-#                        point — whose basis is re-orthonormalised as a whole, like the reference does every iteration —
-# Healthy runs measure 1e-15 .. 1.3e-12 (fp64) / 1e-6 .. 1e-5 (fp32) (profiles/r04_guard_scan.jsonl); two copies of one
-# eigenpair give 1.
-GUARD_GOOD = {torch.float64: 1e-10, torch.float32: 5e-5}
-GUARD_BAD = {torch.float64: 1e-8, torch.float32: 5e-4}
-GUARD_MAX_REDO = 3
 
 
 def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn", max_addition=None,
@@ -794,36 +702,6 @@ def _plan_groups(A, whole, M, B, N, p, dtype, device, precond, overlap, groups, 
     plan.two, plan.ngrp, plan.reserve_cus, plan.spans, plan.ops, plan.streams = two, ngrp, reserve_cus, spans, ops, streams
     plan.k1_streams, plan.k1_sched, plan.distributed = k1_streams, k1_sched, distributed
     return plan
-
-
-def _preconditioner(precond, whole, M, bdims, B, N, dtype, device):
-    """(extension; the reference has none, symeig.py:206-207) the preconditioner of the new directions in the form the
-    groups take it: None, ("diag", diag A, diag M or None) or ("op", panel operator)."""
-    if precond is None:
-        return None
-    from xitorch_amd.linop import LinearOperator as _LinOp
-    if isinstance(precond, str):
-        if precond.lower() not in ("diag", "jacobi", "davidson"):
-            raise RuntimeError("Unknown davidson preconditioner: %s" % precond)
-        dA = whole.diagonal()
-        dM = PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
-        return ("diag", dA, dM)
-    if isinstance(precond, torch.Tensor):
-        if precond.shape[-1] != N:
-            raise RuntimeError("precond diagonal must have shape (*batch, %d), got %s" % (N, tuple(precond.shape)))
-        dA = precond.to(device=device, dtype=dtype).expand(*bdims, N).reshape(B, N).contiguous()
-        dM = PanelOperator(M, bdims, B, N).diagonal() if M is not None else None
-        return ("diag", dA, dM)
-    if isinstance(precond, _LinOp):
-        return ("op", PanelOperator(precond, bdims, B, N))
-    raise TypeError("precond must be None, 'diag', a tensor or a LinearOperator, got %s" % type(precond))
-
-
-def _pc_slice(pc_full, b0, b1):
-    if pc_full is None or pc_full[0] == "op":
-        return pc_full
-    cut = lambda t: None if t is None else (t if t.shape[0] == 1 else t[b0:b1])
-    return ("diag", cut(pc_full[1]), cut(pc_full[2]))
 
 
 def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn", max_addition=None,
@@ -1138,49 +1016,6 @@ def _davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn"
 
 
 davidson.__doc__ = _davidson.__doc__ + "\n    (" + davidson.__doc__ + ")\n"
-
-
-# orders / widths the native dense eigensolvers serve (K3g: xk_eigh_big.hip; below 129 / 17 also the LDS kernels)
-EXACTEIG_NATIVE_MAX_N = K.SMALL_EIGH_BIG_MAX_K
-EXACTEIG_NATIVE_MAX_P = K.SMALL_EIGH_BIG_MAX_P
-
-
-def _native_dense_ok(mat, neig):
-    n = mat.shape[-1]
-    nb = mat.numel() // max(1, n * n)
-    # (beyond order 1024 the native form is ahead of the library from 16 matrices on only: K3G_MAX_K)
-    return (mat.is_cuda and mat.dtype in (torch.float64, torch.float32) and 8 <= n <= EXACTEIG_NATIVE_MAX_N
-            and n <= K3G_MAX_K[0 if nb >= 16 else 1]
-            and 1 <= neig <= min(EXACTEIG_NATIVE_MAX_P, n) and mat.numel() > 0
-            and K.small_eigh_big_ok(n, neig, mat.dtype))
-
-
-def native_partial_eigh(mat, neig, mode):
-    """Lowest / uppermost ``neig`` eigenpairs of the dense symmetric matrices ``mat (*B, n, n)`` on the native HIP
-    eigensolvers — Householder tridiagonalisation, bisection, inverse iteration, back-transformation: K3t (LDS-resident,
-    n <= 128, neig <= 16) or K3g (global-memory work matrix, n <= 1536, neig <= 256).  Only the wanted pairs are computed
-    (the reference's exacteig computes all n and slices, symeig.py:22-24,255-264).  Returns ``evals (*B, neig)``
-    ascending and ``evecs (*B, n, neig)``; members whose self-check flags the result are redone on
-    ``torch.linalg.eigh``."""
-    bdims, n = mat.shape[:-2], mat.shape[-1]
-    T = mat.reshape(-1, n, n)
-    if T.stride(-1) != 1:
-        T = T.contiguous()
-    upp = (mode != "lowest")
-    if n <= K.SMALL_EIGH_MAX_K and neig <= K.SMALL_EIGH_MAX_P and n >= K.SMALL_EIGH_TRI_MIN_K and \
-            K.small_eigh_tri_ok(n, neig, T.dtype):
-        lam, Yt, flag = K.small_eigh(T, n, neig, uppest=upp, method="tri")
-    else:
-        lam, Yt, flag = K.small_eigh_big(T, n, neig, uppest=upp)
-    X = Yt.transpose(1, 2)
-    if int(flag.max().item()) != 0:                   # (rare) self-check failed somewhere: those members on the library
-        bad = torch.nonzero(flag, as_tuple=False).flatten()
-        l2, U2 = torch.linalg.eigh(T[bad])
-        l2, U2 = take_eigpairs(l2, U2, neig, mode)
-        lam = lam.clone()
-        X = X.clone()
-        lam[bad], X[bad] = l2, U2
-    return lam.reshape(*bdims, neig), X.reshape(*bdims, n, neig)
 
 
 class _NativeEigh(torch.autograd.Function):

@@ -17,51 +17,11 @@ import torch
 from xitorch_amd import kernels as K
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
-from xitorch_amd.linalg._panel import PanelOperator, batch_count, real_dtype, require_hip
-from xitorch_amd.linalg.native_eig import _initial_block, _shift_rel
+from xitorch_amd.linalg._panel import PanelOperator, batch_count, require_hip
+# (herm_partial_eigh and _shift_rel: re-exported under the names the tests and scripts know)
+from xitorch_amd.linalg._block import ComplexBlockOps, herm_partial_eigh, _initial_block, _shift_rel
 
 __all__ = ["davidson", "herm_partial_eigh"]
-
-
-def herm_partial_eigh(T, k, p, mode, counts=None):
-    """Lowest / uppermost p eigenpairs of the Hermitian (B, >=k, >=k) complex T[:, :k, :k]: lam (B, p) real
-    ascending, Y (B, k, p) complex.  Native kernel inside its range, members whose self-check fails redone on
-    torch.linalg.eigh, the library beyond the range; `counts` ({"rr_native": .., "rr_library": ..}) counts the calls
-    served each way (a call with any redone member counts as a library call)."""
-    B = T.shape[0]
-    if K.herm_eigh_ok(k, p):
-        lam, Yt, flag = K.herm_eigh(T, k, p, uppest=(mode != "lowest"))
-        Y = Yt.transpose(1, 2)
-        if int(flag.max().item()) == 0:
-            if counts is not None:
-                counts["rr_native"] += 1
-            return lam, Y
-        bad = torch.nonzero(flag, as_tuple=False).flatten()
-        l2, U2 = _library_eigh(T[bad, :k, :k], p, mode)
-        lam, Y = lam.clone(), Y.clone()
-        lam[bad], Y[bad] = l2, U2
-    else:
-        lam, Y = _library_eigh(T[:B, :k, :k], p, mode)
-    if counts is not None:
-        counts["rr_library"] += 1
-    return lam, Y
-
-
-def _library_eigh(T, p, mode):
-    lam, U = torch.linalg.eigh(T)                     # (lower triangle, like the kernel)
-    if mode == "lowest":
-        return lam[..., :p].contiguous(), U[..., :p]
-    return lam[..., -p:].contiguous(), U[..., -p:]
-
-
-def _gram(Vk, W):
-    """C[b, i, c] = sum_n conj(Vk[b, i, n]) W[b, c, n]  (B, k, q): V^H W on K1 with the basis as the matrix"""
-    return K.dense_mm_complex(Vk, W, conj_io=True).transpose(1, 2)
-
-
-def _combine(Vk, C):
-    """out[b, c, :] = sum_i C[b, i, c] Vk[b, i, :]  (B, q, N): the projection V C on K1"""
-    return K.dense_mm_complex(Vk, C.transpose(1, 2).contiguous(), adjoint=True, conj_io=True)
 
 
 class _Basis:
@@ -89,9 +49,6 @@ class _Basis:
             if MV is not None:
                 MV[:, :k].copy_(self.MV[:, :k])
         self.V, self.AV, self.MV, self.T, self.cap = V, AV, MV, T, cap
-
-    def mv(self, hi):
-        return self.MV[:, :hi] if self.with_m else self.V[:, :hi]
 
 
 def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn", max_addition=None, min_eps=1e-6,
@@ -122,11 +79,10 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
                                  "xk_herm_cholqr)" % K.HERM_CHOLQR_MAX_Q)
     bdims = list(A.shape[:-2]) if M is None else list(bcast_shape(A.shape[:-2], M.shape[:-2]))
     B = batch_count(bdims)
-    rdtype = real_dtype(dtype)
     opA = PanelOperator(A, bdims, B, N)
     opM = PanelOperator(M, bdims, B, N) if M is not None else None
-    counts = {"rr_native": 0, "rr_library": 0}
-    info = torch.zeros((B,), dtype=torch.int32, device=device)
+    ops = ComplexBlockOps(B, N, p, dtype, device)
+    counts, info = ops.counts, ops.info
 
     def apply(op, X):
         out = torch.empty_like(X)
@@ -134,15 +90,11 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
         return out
 
     def orthonormalise(W, bas, k):
-        """W (B, q, N) -> (W, M W): (M-)orthonormal, (M-)orthogonal to the first k basis vectors"""
-        q = W.shape[1]
-        MW = None
-        for rnd in range(2):
-            if k > 0:
-                C = _gram(bas.mv(k), W)                       # (MV)^H W
-                W = W - _combine(bas.V[:, :k], C)
-            MW = apply(opM, W) if opM is not None else None
-            K.herm_cholqr(W, info, MW=MW, shift_rel=_shift_rel(N, q, rdtype) if (rnd == 0 and k > 0) else 0.0)
+        """W (B, q, N), a fresh block -> (W, M W): (M-)orthonormal, (M-)orthogonal to the first k basis vectors: two
+        passes, M W recomputed after each projection, the first pass shifted when there is a basis to project against"""
+        MW = torch.empty_like(W) if opM is not None else None
+        ops.orth_block(W, bas.V[:, :k] if k > 0 else None, 2, info, k > 0, MW=MW,
+                       MV=bas.MV[:, :k] if opM is not None and k > 0 else None, opM=opM)
         return W, MW
 
     V0p = _initial_block(v_init, V0, bdims, B, N, nguess, dtype, device, rng_device)      # (B, nguess, N)
@@ -155,7 +107,7 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
     if MW is not None:
         bas.MV[:, :k].copy_(MW)
     bas.AV[:, :k].copy_(apply(opA, W))
-    bas.T[:, :k, :k].copy_(_gram(bas.V[:, :k], bas.AV[:, :k]))
+    bas.T[:, :k, :k].copy_(ops.gram(bas.V[:, :k], bas.AV[:, :k]))
     bas.k = k
 
     Xs = [torch.empty((B, p, N), dtype=dtype, device=device) for _ in range(2)]
@@ -198,10 +150,10 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
         bas.AV[:, k:k + nadd].copy_(AW)
         if MW is not None:
             bas.MV[:, k:k + nadd].copy_(MW)
-        Tcol = _gram(bas.V[:, :k], AW)                       # (B, k, nadd) = V^H A W
+        Tcol = ops.gram(bas.V[:, :k], AW)                       # (B, k, nadd) = V^H A W
         bas.T[:, :k, k:k + nadd].copy_(Tcol)
         bas.T[:, k:k + nadd, :k].copy_(Tcol.transpose(1, 2).conj())
-        bas.T[:, k:k + nadd, k:k + nadd].copy_(_gram(W, AW))
+        bas.T[:, k:k + nadd, k:k + nadd].copy_(ops.gram(W, AW))
         k += nadd
         bas.k = k
     if best_slot < 0:

@@ -38,44 +38,34 @@ import warnings
 import torch
 from xitorch_amd import kernels as K
 from xitorch_amd._util import ConvergenceWarning
-from xitorch_amd.linalg._panel import PanelOperator, pad_len, real_dtype, require_hip
+from xitorch_amd.linalg._panel import PanelOperator, real_dtype, require_hip
+from xitorch_amd.linalg._block import block_ops, GUARD_BAD, GUARD_MAX_REDO, _preconditioner
 from xitorch_amd.linalg import host_eig
 from xitorch_amd.linalg.host_eig import lob_cp, lob_dependent_columns
 
 __all__ = ["lobpcg"]
 
 
-class _Block:
-    """the three stacks and what the iteration does to them; the subclasses supply the kernels of their dtype"""
+class _Stacks:
+    """the three stacks S = [X | P | W], A S and M S on the block layer, and the rotation kernel's partial sums"""
 
-    def __init__(self, Bt, N, w, neig, dtype, device, with_m):
-        self.Bt, self.N, self.w, self.neig, self.dtype, self.device = Bt, N, w, neig, dtype, device
-        self.rdtype = real_dtype(dtype)
+    def __init__(self, ops, neig, with_m):
+        self.ops, self.w, self.neig = ops, ops.w, neig
         self.nalloc = 0                                   # panel buffers allocated, in units of (Bt, w, ld)
-        self.S = self.stack()
-        self.AS = self.stack()
-        self.MS = self.stack() if with_m else None
-        self.info = torch.zeros((Bt,), dtype=torch.int32, device=device)
-        nblk = K.lobpcg_blocks(N, dtype)
-        self.Pnorm = torch.zeros((Bt, w, nblk), dtype=torch.float64, device=device)
-        self.Pmax = torch.zeros((Bt, nblk), dtype=torch.float64, device=device)
-        self.small_eigh = "native"
-        self.zero_lam = self.dabs = None                  # the Jacobi preconditioner's tables, made on first use
+        self.S = self.panels(3)
+        self.AS = self.panels(3)
+        self.MS = self.panels(3) if with_m else None
+        nblk = K.lobpcg_blocks(ops.N, ops.dtype)
+        self.Pnorm = torch.zeros((ops.Bt, self.w, nblk), dtype=torch.float64, device=ops.device)
+        self.Pmax = torch.zeros((ops.Bt, nblk), dtype=torch.float64, device=ops.device)
 
-    def stack(self):
-        self.nalloc += 3
-        return torch.zeros((self.Bt, 3 * self.w, self.ld), dtype=self.dtype, device=self.device)
-
-    def panel(self):
-        self.nalloc += 1
-        return torch.zeros((self.Bt, self.w, self.ld), dtype=self.dtype, device=self.device)
-
-    def rows(self, stack, k0):
-        return stack[:, k0:k0 + self.w]
+    def panels(self, n):
+        self.nalloc += n
+        return self.ops.panel(n * self.w)
 
     def rotate(self, C, lam, k, q):
         """the stacks' rows [0, q) <- their combinations by C (Bt, k, q); residual -> S rows [q, q + w)"""
-        K.lobpcg_rotate(self.S, self.AS, self.MS, C, lam.to(torch.float64).contiguous(), k, q, self.w, N=self.N,
+        K.lobpcg_rotate(self.S, self.AS, self.MS, C, lam.to(torch.float64).contiguous(), k, q, self.w, N=self.ops.N,
                         Pnorm=self.Pnorm, Pmax=self.Pmax)
 
     def resid_max(self, q):
@@ -84,142 +74,17 @@ class _Block:
         residual rows (a max-norm reduction, no temporary panel)."""
         if self.neig == self.w:
             return self.Pmax.amax(dim=1)
-        R = self.S[:, q:q + self.neig, :self.N]
+        R = self.S[:, q:q + self.neig, :self.ops.N]
         return torch.linalg.vector_norm(R, ord=float("inf"), dim=(1, 2)).to(torch.float64)
 
     def orth(self, k0, passes, opM):
         """rows [k0, k0 + w) of S M-orthonormal and M-orthogonal to rows [0, k0); with M the rows of MS follow (M is
-        applied once).  The Cholesky flags land in self.info (sticky)."""
-        raise NotImplementedError
-
-
-class _RealBlock(_Block):
-    """fp64 / fp32: zero-padded (Bt, 3w, pad_len(N)) stacks on the Davidson chain kernels"""
-
-    def __init__(self, Bt, N, w, neig, dtype, device, with_m):
-        self.ld = pad_len(N)
-        super().__init__(Bt, N, w, neig, dtype, device, with_m)
-        self.Cs = torch.empty((Bt * max(w, 32) * max(2 * w, 32),), dtype=dtype, device=device)
-        self.Wq = torch.empty((Bt * 32 * 32,), dtype=dtype, device=device)
-        self.rmax = torch.zeros((Bt,), dtype=dtype, device=device)
-        self.orth_g = torch.zeros((Bt,), dtype=dtype, device=device)
-        self.status = torch.zeros((5,), dtype=torch.float64, device=device)
-
-    def load(self, V0p):
-        self.S[:, :self.w, :self.N].copy_(V0p)
-
-    def gram(self, Pa, Pb):
-        """G[b, i, c] = <Pa_i, Pb_c>"""
-        return K.dense_mm(Pa[:, :, :self.N], Pb[:, :, :self.N]).transpose(1, 2)
-
-    def orth(self, k0, passes, opM):
-        N, w = self.N, self.w
-        if self.MS is None:
-            K.davidson_orth(self.S, N, k0, w, self.Cs, self.Wq, self.info, passes=passes)
-            return
-        from xitorch_amd.linalg.native_eig import _shift_rel
-        W, MW = self.rows(self.S, k0), self.rows(self.MS, k0)
-        opM.apply(W, MW)
-        Wq = self.Wq[:self.Bt * w * w].view(self.Bt, w, w)
-        for r in range(passes):
-            if k0 > 0:
-                C = K.dense_mm(self.MS[:, :k0, :N], W[:, :, :N])             # C[b, c, a] = <M S_a, W_c>
-                K.lincomb(self.S, C, W, k0, w, coef_layout="ca", alpha=-1.0, beta=1.0)
-                K.lincomb(self.MS, C, MW, k0, w, coef_layout="ca", alpha=-1.0, beta=1.0)
-            G = K.dense_mm(W[:, :, :N], MW[:, :, :N])
-            if r == 0 and passes > 1:
-                tr = torch.diagonal(G, dim1=-2, dim2=-1).sum(-1)
-                G = G + (_shift_rel(N, w, self.dtype) * tr)[:, None, None] * torch.eye(w, dtype=G.dtype,
-                                                                                         device=G.device)
-            K.panel_chol(G, Wq, self.info, w)
-            K.panel_transform(W, Wq, w)
-            K.panel_transform(MW, Wq, w)
-
-    def eigh(self, T, n, p):
-        """(mu (Bt, p) ascending, Y (Bt, n, p)) of the symmetric (Bt, n, n) T on the native dense solvers"""
-        from xitorch_amd.linalg.native_eig import native_partial_eigh
-        if n >= 8:
-            return native_partial_eigh(T, p, "lowest")
-        mu, Yt, _ = K.small_eigh(T, n, p)                                    # LDS Jacobi kernel (tiny blocks)
-        return mu, Yt.transpose(1, 2)
-
-    def precond_diag(self, R, d):
-        """R <- R / |d| (Jacobi; xk_diag_precond with a zero shift table)"""
-        if self.zero_lam is None:
-            self.zero_lam = torch.zeros((self.Bt, self.w), dtype=self.dtype, device=self.device)
-            self.dabs = d.abs().contiguous()
-        K.diag_precond(R, self.dabs, self.zero_lam, self.w)
+        applied once).  The Cholesky flags land in ops.info (sticky)."""
+        self.ops.orth(self.S, k0, self.w, passes, self.ops.info, MS=self.MS, opM=opM)
 
     def status_read(self, q):
         """[max|resid| over the wanted columns, Cholesky flag, guard] of X = rows [0, w): the one host read"""
-        self.rmax.copy_(self.resid_max(q))
-        K.ritz_guard(self.S, self.orth_g, self.w, self.ld, MX=self.MS)
-        K.group_status(self.rmax, self.info, None, self.status, orth=self.orth_g)
-        st = self.status.tolist()
-        return st[0], st[1], st[4]
-
-    def result(self, X, bdims):
-        return X[:, :self.neig, :self.N].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
-
-
-class _ComplexBlock(_Block):
-    """complex128 / complex64: (Bt, 3w, N) stacks on the Hermitian Davidson kernels (xk_herm_*)"""
-
-    def __init__(self, Bt, N, w, neig, dtype, device, with_m):
-        self.ld = N
-        super().__init__(Bt, N, w, neig, dtype, device, with_m)
-        self.counts = {"rr_native": 0, "rr_library": 0}
-        self.eye = torch.eye(w, dtype=dtype, device=device)
-
-    def load(self, V0p):
-        self.S[:, :self.w].copy_(V0p)
-
-    def gram(self, Pa, Pb):
-        from xitorch_amd.linalg.native_eig_herm import _gram
-        return _gram(Pa, Pb)
-
-    def orth(self, k0, passes, opM):
-        from xitorch_amd.linalg.native_eig_herm import _shift_rel, _gram, _combine
-        w = self.w
-        W = self.rows(self.S, k0)
-        MW = None
-        if self.MS is not None:
-            MW = self.rows(self.MS, k0)
-            opM.apply(W, MW)
-        for r in range(passes):
-            if k0 > 0:
-                C = _gram((self.MS if self.MS is not None else self.S)[:, :k0], W).contiguous()
-                W.sub_(_combine(self.S[:, :k0], C))
-                if MW is not None:
-                    MW.sub_(_combine(self.MS[:, :k0], C))
-            K.herm_cholqr(W, self.info, MW=MW,
-                          shift_rel=_shift_rel(self.N, w, self.rdtype) if (r == 0 and passes > 1) else 0.0)
-
-    def eigh(self, T, n, p):
-        from xitorch_amd.linalg.native_eig_herm import herm_partial_eigh
-        mu, Y = herm_partial_eigh(T, n, p, "lowest", self.counts)           # the library where chebfsi uses it: p > 16
-        if self.counts["rr_library"]:
-            self.small_eigh = "library"
-        return mu, Y
-
-    def precond_diag(self, R, d):
-        """R <- R / |d| (Jacobi): the real kernel xk_diag_precond on the interleaved storage, every diagonal entry
-        taken twice, with a zero shift table"""
-        if self.zero_lam is None:
-            self.zero_lam = torch.zeros((self.Bt, self.w), dtype=self.rdtype, device=self.device)
-            self.dabs = d.abs().to(self.rdtype).repeat_interleave(2, dim=-1).contiguous()
-        Rr = torch.view_as_real(R).reshape(R.shape[0], R.shape[1], 2 * R.shape[2])
-        K.diag_precond(Rr, self.dabs, self.zero_lam, self.w)
-
-    def status_read(self, q):
-        X = self.S[:, :self.w]
-        MX = self.MS[:, :self.w] if self.MS is not None else X
-        guard = (self.gram(X, MX) - self.eye).abs().max().to(torch.float64)
-        st = torch.stack((self.resid_max(q).max(), self.info.max().to(torch.float64), guard)).tolist()
-        return st[0], st[1], st[2]
-
-    def result(self, X, bdims):
-        return X[:, :self.neig].transpose(-2, -1).reshape(*bdims, self.N, self.neig)
+        return self.ops.status(self.S, self.w, self.resid_max(q), self.ops.info, MX=self.MS)
 
 
 def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, precond=None, V0=None, v_init="randn",
@@ -263,7 +128,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
 
     Not built: locking / deflation of converged columns, batch sharding, an MFMA form of the rotation.
     """
-    from xitorch_amd.linalg.native_eig import exacteig, GUARD_BAD, GUARD_MAX_REDO, _preconditioner
+    from xitorch_amd.linalg.native_eig import exacteig
     device = torch.device(A.device)
     if device.type == "cpu":
         # device dispatch (see native_eig.davidson): an operator in HOST memory is served by host_eig.py
@@ -289,11 +154,12 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     if trace is not None and trace.get("k1_events") is not None:
         op.events = trace["k1_events"]
     pc = _preconditioner(precond, op, M, bdims, Bt, N, dtype, device)
-    blk = (_ComplexBlock if dtype.is_complex else _RealBlock)(Bt, N, w, neig, dtype, device, M is not None)
+    ops = block_ops(Bt, N, w, dtype, device, kmax=2 * w)
+    blk = _Stacks(ops, neig, M is not None)
     S, AS, MS = blk.S, blk.AS, blk.MS
-    best_X = blk.panel()
-    spare = blk.panel()                    # random directions, drawn once: what replaces a column without a direction
-    scratch = blk.panel() if pc is not None and pc[0] == "op" else None            # the preconditioner's output
+    best_X = blk.panels(1)
+    spare = blk.panels(1)                  # random directions, drawn once: what replaces a column without a direction
+    scratch = blk.panels(1) if pc is not None and pc[0] == "op" else None          # the preconditioner's output
     ndraw, redraws, restarts, nfail = 0, 0, 0, 0
     bad_cols = torch.zeros((), dtype=torch.int64, device=device)
 
@@ -304,13 +170,11 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
         dst[:, :, :N].copy_(R)
 
     def chol_flag():
-        return int(blk.info.max().item())
+        return int(ops.info.max().item())
 
     def ritz_on_x():
         """Rayleigh-Ritz on X alone (rows [0, w)); the residual lands in rows [w, 2w)"""
-        T = blk.gram(S[:, :w], AS[:, :w])
-        T = ((T + T.transpose(1, 2).conj()) * (0.5 * sign)).contiguous()
-        mu, Y = blk.eigh(T, w, w)
+        mu, Y = ops.eigh_lowest(ops.rr_matrix(S[:, :w], AS[:, :w], sign), w, w)
         lam = mu * sign
         blk.rotate(Y, lam, w, w)
         return lam
@@ -318,23 +182,23 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     # ---- start: M-orthonormal block, Rayleigh-Ritz on it alone
     random_into(spare)
     V0p = host_eig._cheb_start_block(v_init, V0, bdims, Bt, N, w, dtype, device, rng_device)
-    blk.load(V0p)
-    blk.info.zero_()
+    ops.load(S[:, :w], V0p)
+    ops.info.zero_()
     blk.orth(0, 2, opM)
     _, flag, guard = blk.status_read(w)
     if flag != 0 or not guard <= gbad:
         # dependent start vectors (the shifted first pass hides them from the Cholesky flag; the guard sees them): the
         # columns a Cholesky factorisation of the small Gram matrix (on the host) finds dependent are drawn afresh and
         # the block gets three passes; a second failure raises
-        blk.load(V0p)
+        ops.load(S[:, :w], V0p)
         X0 = S[:, :w]
         if opM is not None:
             opM.apply(X0, MS[:, :w])
-        G = blk.gram(X0, MS[:, :w] if opM is not None else X0)
+        G = ops.gram(X0, MS[:, :w] if opM is not None else X0)
         bad = lob_dependent_columns(G, rdt).to(device)
         redraws += int(bad.sum())
         X0.copy_(torch.where(bad[:, :, None], spare, X0))
-        blk.info.zero_()
+        ops.info.zero_()
         blk.orth(0, 3, opM)
         if chol_flag() != 0:
             raise RuntimeError("lobpcg: the start block is rank deficient (linearly dependent start vectors)")
@@ -367,7 +231,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
             nrm = torch.sqrt(blk.Pnorm.sum(dim=-1))
         else:
             if pc[0] == "diag":
-                blk.precond_diag(R, pc[1])
+                ops.precond_diag(R, pc[1])
             else:
                 pc[1].apply(R, scratch)
                 R.copy_(scratch)
@@ -377,13 +241,11 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
         inv = torch.where(bad, torch.ones_like(nrm), 1.0 / torch.where(bad, torch.ones_like(nrm), nrm)).to(rdt)
         R.mul_(inv[:, :, None])
         torch.where(bad[:, :, None], spare, R, out=R)
-        blk.info.zero_()
+        ops.info.zero_()
         blk.orth(q, 2, opM)
         k = q + w
         op.apply(S[:, q:k], AS[:, q:k])
-        T = blk.gram(S[:, :k], AS[:, :k])                 # recomputed from the stacks every iteration
-        T = ((T + T.transpose(1, 2).conj()) * (0.5 * sign)).contiguous()
-        mu, Cx = blk.eigh(T, k, w)
+        mu, Cx = ops.eigh_lowest(ops.rr_matrix(S[:, :k], AS[:, :k], sign), k, w)   # T_S recomputed from the stacks
         lam = mu * sign
         C = torch.cat((Cx, lob_cp(Cx, w)), dim=-1)
         blk.rotate(C, lam, k, 2 * w)
@@ -399,7 +261,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
             if nfail > GUARD_MAX_REDO:
                 raise RuntimeError("xitorch_amd lobpcg: the block lost its orthonormality %d times (max|X^H M X - I| = "
                                    "%.2e, Cholesky flag %d, at iteration %d)" % (nfail, guard, int(flag), niter))
-            blk.info.zero_()
+            ops.info.zero_()
             if flag != 0:
                 # (the stacks hold combinations of a W that was not orthonormal: start again from the best block)
                 S[:, :w].copy_(best_X)
@@ -421,10 +283,10 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
         if dtype.is_complex and op.kind == "dense":
             kernel = "K1"
         trace.update(niter=niter, napply=op.napply, w=w, resid_history=history, best_resid=best_resid,
-                     restarts=restarts, redraws=redraws + int(bad_cols.item()), small_eigh=blk.small_eigh,
+                     restarts=restarts, redraws=redraws + int(bad_cols.item()), small_eigh=ops.small_eigh,
                      panel_kernel=kernel, panel_buffers=blk.nalloc, torch_applies=op.torch_applies)
     evals = best_lam.to(rdt).reshape(*bdims, neig)
-    evecs = blk.result(best_X, bdims)
+    evecs = ops.result(best_X, neig, bdims)
     if mode != "lowest":
         evals, evecs = evals.flip(-1), evecs.flip(-1)
     return evals, evecs
