@@ -639,6 +639,36 @@ int xk_cheb_step_c64(const float* AY, long ldA, long sA, const float* Y, long ld
                      long ldP, long sP, float* out, long ldO, long sO, const double* coef, int Bt, int p, int N,
                      void* stream);
 
+/* ---- Clenshaw step of a Chebyshev band-pass filter (extension: Li, Xi, Vecharynski, Yang, Saad 2016; symeig
+ * mode "nearest"; new symbols only) ----
+ * Panels as for xk_cheb_step: (Bt, p, ld*) arrays, each of the five with its own pitch ld* >= N and batch stride
+ * s* >= 0 (elements; complex elements for _c128 / _c64, which address interleaved (re, im) storage).  For every
+ * b < Bt, c < p, n < N
+ *     out[b,c,n] = ((coef[4b] * AY[b,c,n] + coef[4b+1] * Y[b,c,n]) + coef[4b+2] * Yprev[b,c,n]) + coef[4b+3] * X0[b,c,n]
+ * coef: (Bt, 4) DOUBLES on the device (alpha, beta, gamma, delta per operator, real for every suffix), read by the
+ * kernel: no host synchronisation.  _f64 / _c128 evaluate in double; _f32 / _c64 round each coefficient once to float
+ * and evaluate in float; the sum is taken left to right as written, products may be contracted into FMAs.
+ * gamma == 0.0 exactly (either sign): Yprev[b] is not read (it may hold NaN / Inf) and its term is absent.
+ * out may BE Yprev (same pointer, pitch and batch stride) or lie apart from it.  XK_ERR_ARG, nothing launched, nothing
+ * written: the address range of out intersects that of AY, Y or X0 (or that of a Yprev it is not identical to),
+ * N <= 0, Bt <= 0, p <= 0, a pitch below N, a negative stride, a NULL pointer, rows of out that overlap each other
+ * (Bt > 1 and sO < (p - 1) * ldO + N).  Only out[b, c, :N] is written (pads stay).  All stores are ordinary vector
+ * stores.  Every base 16 B aligned and every pitch / batch stride a multiple of the 16 B vector: vector form (16 B
+ * non-temporal loads, 4 per lane and array in flight); any other layout: scalar form, same result contract.
+ * 5 Bt p N s bytes (4 where gamma == 0). */
+int xk_cheb_clenshaw_f64(const double* AY, long ldA, long sA, const double* Y, long ldY, long sY, const double* Yprev,
+                         long ldP, long sP, const double* X0, long ldX, long sX, double* out, long ldO, long sO,
+                         const double* coef, int Bt, int p, int N, void* stream);
+int xk_cheb_clenshaw_f32(const float* AY, long ldA, long sA, const float* Y, long ldY, long sY, const float* Yprev,
+                         long ldP, long sP, const float* X0, long ldX, long sX, float* out, long ldO, long sO,
+                         const double* coef, int Bt, int p, int N, void* stream);
+int xk_cheb_clenshaw_c128(const double* AY, long ldA, long sA, const double* Y, long ldY, long sY, const double* Yprev,
+                          long ldP, long sP, const double* X0, long ldX, long sX, double* out, long ldO, long sO,
+                          const double* coef, int Bt, int p, int N, void* stream);
+int xk_cheb_clenshaw_c64(const float* AY, long ldA, long sA, const float* Y, long ldY, long sY, const float* Yprev,
+                         long ldP, long sP, const float* X0, long ldX, long sX, float* out, long ldO, long sO,
+                         const double* coef, int Bt, int p, int N, void* stream);
+
 /* ---- LOBPCG: the in-place rotation of the three panel stacks (extension: symeig method "lobpcg"; new symbols only) --
  * S, AS and (may be NULL) MS are (Bt, rows, ld*) stacks [X | P | W] of the driver: every row a contiguous run of N
  * elements, pitch ld* >= N, stack stride s* (elements; complex elements for _c128 / _c64, interleaved storage).

@@ -705,6 +705,41 @@ def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
     return rc if raw else out
 
 
+def cheb_clenshaw(AY, Y, Yprev, X0, coef, out=None, N=None, raw=False):
+    """out[b,c,:N] = ((coef[b,0] * AY + coef[b,1] * Y) + coef[b,2] * Yprev) + coef[b,3] * X0  (xk_cheb_clenshaw_*): the
+    Clenshaw step of a Chebyshev band-pass filter on (Bt, p, ld) panels of one dtype (real or complex), unit stride
+    along the vector.  coef: (Bt, 4) float64 on the device, read by the kernel (no host synchronisation).  out: None =
+    Yprev itself (the driver's ring: the oldest panel is overwritten), or a panel apart from it; never AY, Y or X0.
+    Where coef[b,2] == 0 exactly, Yprev[b] is not read.  N: vector length (default: the panels' whole last dimension);
+    only out[:, :, :N] is written.  raw=True returns the status code instead of raising (tests of the argument
+    checks)."""
+    if out is None:
+        out = Yprev
+    panels = (AY, Y, Yprev, X0, out)
+    for t in panels:
+        require_device(t, "panel")
+        if t.dim() != 3 or t.shape[:2] != AY.shape[:2] or t.dtype != AY.dtype or (t.shape[2] > 1 and t.stride(2) != 1):
+            raise _capi.NativeLibraryError("cheb_clenshaw: panels must be (Bt, p, ld) of one dtype and shape, unit "
+                                           "stride along the vector")
+    if AY.is_complex():
+        _require_resolved("cheb_clenshaw", *panels)
+    Bt, p = AY.shape[0], AY.shape[1]
+    require_device(coef, "coefficients")
+    if coef.dtype != torch.float64 or coef.shape != (Bt, 4) or not coef.is_contiguous():
+        raise _capi.NativeLibraryError("cheb_clenshaw: coef must be a contiguous (Bt, 4) float64 tensor")
+    if N is None:
+        N = min(t.shape[2] for t in panels)
+    elif any(t.shape[2] < N for t in panels) and N > 0:
+        raise _capi.NativeLibraryError("cheb_clenshaw: a panel is shorter than N = %d" % N)
+    args = []
+    for t in panels:
+        # (a one-vector panel / a one-member batch may carry any stride there)
+        args += [ptr(t), t.stride(1) if (p > 1 or t.stride(1) >= t.shape[2]) else t.shape[2],
+                 t.stride(0) if Bt > 1 else 0]
+    rc = call("xk_cheb_clenshaw", AY.dtype, *args, ptr(coef), Bt, p, int(N), raw=raw)
+    return rc if raw else out
+
+
 # --------------------------------------------------------------------------- LOBPCG rotation (xk_lobpcg.hip)
 def lobpcg_max_rows():
     """largest order k of the Rayleigh-Ritz problem `lobpcg_rotate` accepts"""

@@ -22,9 +22,19 @@ __all__ = ["RealBlockOps", "ComplexBlockOps", "block_ops", "cholqr_step", "nativ
            "take_eigpairs", "GUARD_GOOD", "GUARD_BAD", "GUARD_MAX_REDO"]
 
 
-def take_eigpairs(evals, evecs, neig, mode):
+def take_eigpairs(evals, evecs, neig, mode, sigma=None):
     """First (``lowest``) or last (``uppest``) ``neig`` pairs of an ascending ``eigh`` result; the
-    returned eigenvalues are ascending in both modes (reference: symeig.py:255-264)."""
+    returned eigenvalues are ascending in both modes (reference: symeig.py:255-264).  ``nearest`` (extension): the
+    ``neig`` pairs whose eigenvalues are nearest ``sigma`` (a number or a real tensor broadcastable to the batch
+    dimensions; no gradient flows to it), ascending as well."""
+    if mode == "nearest":
+        if sigma is None:
+            raise ValueError("mode='nearest' needs the target: pass sigma=")
+        s = sigma.detach() if isinstance(sigma, torch.Tensor) else torch.as_tensor(sigma)
+        s = s.to(device=evals.device, dtype=evals.dtype).expand(evals.shape[:-1]).unsqueeze(-1)
+        idx = torch.argsort((evals.detach() - s).abs(), dim=-1, stable=True)[..., :neig]
+        idx = torch.sort(idx, dim=-1)[0]                     # eigh's order: the picked eigenvalues ascend
+        return torch.gather(evals, -1, idx), torch.gather(evecs, -1, idx.unsqueeze(-2).expand(*evecs.shape[:-1], neig))
     if mode == "lowest":
         return evals[..., :neig], evecs[..., :neig]
     return evals[..., -neig:], evecs[..., -neig:]

@@ -10,6 +10,7 @@ the block; the reference re-factorises the whole basis by CholeskyQR every itera
 same Q in exact arithmetic), and `T = V^H A V` is extended by its new rows instead of being recomputed.  Each HIP kernel
 call of the native driver is the torch expression it computes.  Nothing here imports `oracle/`.
 """
+import math
 import torch
 from xitorch_amd._capi import NativeLibraryError
 from xitorch_amd._util import bcast_shape
@@ -17,7 +18,8 @@ from xitorch_amd.dist import allreduce_max_
 from xitorch_amd.linalg._block import _initial_block, _shard_of_global_batch, _shift_rel, GUARD_BAD, GUARD_MAX_REDO
 
 __all__ = ["davidson", "chebfsi", "cheb_coefficients", "cheb_default_nguard", "gkl", "gkl_default_ncv", "lobpcg",
-           "lobpcg_default_nguard"]
+           "lobpcg_default_nguard", "chebwin_coefficients", "chebwin_jackson", "chebwin_ladder", "chebwin_degree",
+           "chebwin_tail", "chebwin_select"]
 
 calls = {"davidson": 0, "chebfsi": 0, "gkl": 0, "lobpcg": 0}
 
@@ -56,6 +58,7 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
     the all-reduced residual) and `trace`, as in `native_eig.davidson`; the HIP driver's scheduling knobs are accepted
     and have no meaning here; `precond=` / `restart=` (extensions of the HIP driver) are not available."""
     calls["davidson"] += 1
+    refuse_nearest("davidson", mode)
     dev = torch.device(A.device)
     if dev.type != "cpu":
         raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "
@@ -163,6 +166,167 @@ def cheb_coefficients(a, b, a0, degree, sign=1.0):
     return torch.stack(rows, dim=0)
 
 
+# ---- mode="nearest": the Jackson-damped Chebyshev delta filter (Li, Xi, Vecharynski, Yang, Saad, SIAM J. Sci. Comput.
+# 38 (2016) A2512), evaluated by Clenshaw's recurrence; shared by this file's twin and native_chebfsi
+CHEBWIN_FIRST_DEGREE = 20    # degree of the first filter of a run
+CHEBWIN_LADDER_FLOOR = 8     # the ladder of the degree rule: 8, then m <- floor(1.25 m) + 1, ..., max_degree
+_chebwin_tables = {}
+
+
+def refuse_nearest(name, mode):
+    """davidson and lobpcg find an END of the spectrum: asked for interior pairs they would return the uppermost"""
+    if isinstance(mode, str) and mode.lower() == "nearest":
+        raise NotImplementedError("%s: mode='nearest' (interior eigenpairs) is not supported by this method; use "
+                                  "method='chebfsi' (or 'exacteig')" % name)
+
+
+def chebwin_sigma(sigma, bdims, device):
+    """the target of mode="nearest" as a float64 tensor of the batch shape on `device` (no gradient flows to it)"""
+    if sigma is None:
+        raise ValueError("mode='nearest' needs the target: pass sigma= (a number, or a real tensor broadcastable to "
+                         "the batch dimensions)")
+    s = sigma.detach() if isinstance(sigma, torch.Tensor) else torch.as_tensor(sigma)
+    if s.is_complex():
+        raise ValueError("mode='nearest': sigma must be real (the spectrum of a Hermitian operator is)")
+    return s.to(device=device, dtype=torch.float64).expand(tuple(bdims)).contiguous()
+
+
+def chebwin_select(lam, sigma):
+    """(.., w) indices that order the Ritz values lam (.., w) by |lam - sigma| ascending (sigma (..,): the true
+    target, not the clipped centre); torch ops on the values' device, no host read"""
+    return torch.argsort((lam.to(torch.float64) - sigma.unsqueeze(-1)).abs(), dim=-1, stable=True)
+
+
+def chebwin_jackson(m, device=None):
+    """Jackson damping coefficients g_k^m, k = 0 .. m, float64: with a = pi / (m + 2),
+    g_k = sin((k + 1) a) / ((m + 2) sin a) + (1 - (k + 1) / (m + 2)) cos(k a); g_0 = 1"""
+    k = torch.arange(m + 1, dtype=torch.float64, device=device)
+    a = math.pi / (m + 2)
+    return torch.sin((k + 1) * a) / ((m + 2) * math.sin(a)) + (1.0 - (k + 1) / (m + 2)) * torch.cos(k * a)
+
+
+def chebwin_interval(lo, hi):
+    """(c, e, flat) of the interval [lo, hi] (float64 tensors): centre, half width, and the members whose spectrum has
+    no width (a zero operator, a multiple of the identity; also NaN), which get c = lo, e = 1 and the identity filter"""
+    lo, hi = lo.to(torch.float64), hi.to(torch.float64)
+    width = hi - lo
+    flat = ~(width > 1e-14 * torch.maximum(hi.abs(), lo.abs()))
+    c = torch.where(flat, lo, (hi + lo) * 0.5)
+    e = torch.where(flat, torch.ones_like(width), width * 0.5)
+    return c, e, flat
+
+
+def chebwin_angle(x, c, e):
+    """theta = acos((x - c) / e), the argument clipped to [-1, 1]"""
+    return torch.acos(torch.clamp((x.to(torch.float64) - c) / e, -1.0, 1.0))
+
+
+def chebwin_coefficients(lo, hi, sigma_c, m):
+    """Coefficient table of one band-pass filter of degree m >= 1 in Clenshaw form: (m + 1, *S, 4) float64 from the
+    float64 tensors lo, hi, sigma_c of shape S (any device; elementwise ops, no host synchronisation).  With
+    c = (hi + lo) / 2, e = (hi - lo) / 2, t = (lambda - c) / e and theta_s = acos(t(sigma_c)) the filter is
+        p(t) = sum_{k=0..m} c_k T_k(t),   c_k = g_k^m mu_k / norm,   mu_k = (2 - delta_k0) cos(k theta_s),
+    the Jackson-damped Chebyshev expansion of a delta function at sigma_c, normalised to p(t(sigma_c)) = 1.  Row 0 is
+    (0, c_m, 0, 0): b_m = c_m X, one `cheb_step` on its first three entries.  Row j = 1 .. m is the Clenshaw step
+        b_k = alpha (A b_{k+1}) + beta b_{k+1} + gamma b_{k+2} + delta X,   k = m - j,
+    (alpha, beta, gamma, delta) = (2 / e, -2 c / e, -1, c_k) for k >= 1 and (1 / e, -c / e, -1, c_0) for the last one,
+    whose result is p(A) X; gamma = 0 in row 1 (b_{m+1} = 0: the panel is not read).  That is m applies.  A member
+    without spectral width gets the identity: (0, 1, 0, 0), then (0, 0, 0, 1)."""
+    m = int(m)
+    if m < 1:
+        raise ValueError("chebwin_coefficients: the degree must be >= 1, got %d" % m)
+    c, e, flat = chebwin_interval(lo, hi)
+    th = chebwin_angle(sigma_c, c, e)
+    dev = th.device
+    shape = (m + 1,) + (1,) * th.dim()
+    k = torch.arange(m + 1, dtype=torch.float64, device=dev).reshape(shape)
+    cosk = torch.cos(k * th.unsqueeze(0))                               # (m + 1, *S)
+    mu = cosk * 2.0
+    mu[0] = cosk[0]
+    gm = chebwin_jackson(m, dev).reshape(shape) * mu
+    ck = gm / (gm * cosk).sum(dim=0, keepdim=True)                      # p(theta_s) = 1 (the Jackson kernel is > 0)
+    ck = ck.flip(0)                                                     # row j holds c_{m-j}
+    one, zero = torch.ones_like(ck), torch.zeros_like(ck)
+    last = torch.zeros(shape, dtype=torch.bool, device=dev)
+    last[m] = True
+    first = torch.zeros(shape, dtype=torch.bool, device=dev)
+    first[0] = True
+    second = torch.zeros(shape, dtype=torch.bool, device=dev)
+    second[1] = True
+    scale = torch.where(last, one, 2.0 * one) / e.unsqueeze(0)          # 2 / e, the last row 1 / e
+    al = torch.where(first, zero, scale)
+    be = torch.where(first, ck, -scale * c.unsqueeze(0))
+    ga = torch.where(first | second, zero, -one)
+    de = torch.where(first, zero, ck)
+    fl = flat.unsqueeze(0)
+    al = torch.where(fl, zero, al)
+    be = torch.where(fl, torch.where(first, one, zero), be)
+    ga = torch.where(fl, zero, ga)
+    de = torch.where(fl, torch.where(first, zero, one), de)
+    return torch.stack((al, be, ga, de), dim=-1)
+
+
+def chebwin_ladder(max_degree):
+    """the degrees the rule chooses from: 8, then m <- floor(1.25 m) + 1 while below max_degree, then max_degree"""
+    max_degree = int(max_degree)
+    out, m = [], CHEBWIN_LADDER_FLOOR
+    while m < max_degree:
+        out.append(m)
+        m = (5 * m) // 4 + 1
+    out.append(max(1, max_degree))
+    return out
+
+
+def _chebwin_table(max_degree):
+    """(ladder, G) with G (L, K + 1) float64 on the host: row l holds the Jackson coefficients of degree ladder[l],
+    zero beyond it (built once per max_degree)"""
+    key = int(max_degree)
+    if key not in _chebwin_tables:
+        ladder = chebwin_ladder(key)
+        G = torch.zeros((len(ladder), ladder[-1] + 1), dtype=torch.float64)
+        for i, m in enumerate(ladder):
+            G[i, :m + 1] = chebwin_jackson(m)
+        _chebwin_tables[key] = (ladder, G)
+    return _chebwin_tables[key]
+
+
+def chebwin_tail(theta_s, d_ref, max_degree):
+    """(L, *S) float64: max |p_m(theta_s +- d_ref)| of the normalised filter of every ladder degree, by the closed form
+    p_m(theta) = sum_k g_k^m mu_k cos(k theta) / sum_k g_k^m mu_k cos(k theta_s); torch ops on the angles' device"""
+    ladder, G = _chebwin_table(max_degree)
+    G = G.to(theta_s.device)
+    S = theta_s.shape
+    ts, d = theta_s.reshape(1, -1).to(torch.float64), d_ref.reshape(1, -1).to(torch.float64)
+    k = torch.arange(G.shape[1], dtype=torch.float64, device=G.device).reshape(-1, 1)
+    cs = torch.cos(k * ts)
+    mu = cs * 2.0
+    mu[0] = cs[0]
+    peak = torch.matmul(G, mu * cs)
+    up = torch.matmul(G, mu * torch.cos(k * (ts + d))).abs()
+    dn = torch.matmul(G, mu * torch.cos(k * (ts - d))).abs()
+    return (torch.maximum(up, dn) / peak).reshape(len(ladder), *S)
+
+
+def chebwin_degree(theta_s, d_ref, filter_tail, max_degree):
+    """The degree rule: the smallest degree of the ladder whose filter, centred at the angle theta_s, has fallen to
+    `filter_tail` of its peak at the angular distance d_ref on both sides; a batch takes the largest degree any member
+    asks for.  Returns (degree, capped): capped = no degree below max_degree satisfies it (max_degree is then used).
+    ONE host read (the index into the ladder)."""
+    ladder, _G = _chebwin_table(max_degree)
+    ok = chebwin_tail(theta_s, d_ref, max_degree) <= filter_tail
+    ok = ok.reshape(len(ladder), -1)
+    ok[-1] = True
+    idx = int(torch.argmax(ok.to(torch.int32), dim=0).max().item())
+    return ladder[idx], idx == len(ladder) - 1
+
+
+def chebwin_dref(lam_sel, theta_s, c, e, neig, w):
+    """angular distance |theta - theta_s| of the (neig + ceil(nguard / 2))-th nearest block Ritz value (lam_sel (.., w)
+    in the order of `chebwin_select`; the index is clipped to the block)"""
+    idx = min(neig + -(-(w - neig) // 2), w) - 1
+    return (chebwin_angle(lam_sel[..., idx], c, e) - theta_s).abs()
+
+
 def _cheb_check_args(name, M, process_group):
     if M is not None:
         raise NotImplementedError("%s: an overlap operator M is not supported: the Chebyshev filter of A X = M X E acts "
@@ -194,14 +358,140 @@ def _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device):
     return torch.cat((V, extra), dim=1)
 
 
+def _cheb_host_lanczos(apply, bdims, N, dtype, rdt, lanczos_steps):
+    """Ritz values (*bdims, ks) of A, ascending, and the residual norm |f_k| (*bdims,) of a short Lanczos run from the
+    one start vector of `_cheb_lanczos_vector`, float64"""
+    ks = max(2, min(int(lanczos_steps), N - 1))
+    v = _cheb_lanczos_vector(bdims, N, dtype)
+    v = v / torch.linalg.vector_norm(v, dim=-2, keepdim=True)
+    vprev = torch.zeros_like(v)
+    Tl = torch.zeros((*bdims, ks, ks), dtype=torch.float64)
+    beta = torch.zeros((*bdims,), dtype=torch.float64)
+    for j in range(ks):
+        f = apply(v)
+        al = (v.conj() * f).sum(dim=(-2, -1)).real.to(torch.float64)
+        f = f - al.to(rdt)[..., None, None] * v - beta.to(rdt)[..., None, None] * vprev
+        Tl[..., j, j] = al
+        beta = torch.linalg.vector_norm(f, dim=(-2, -1)).to(torch.float64)
+        if j + 1 < ks:
+            Tl[..., j, j + 1] = beta
+            Tl[..., j + 1, j] = beta
+            inv = torch.where(beta > 0, 1.0 / beta, torch.zeros_like(beta))
+            vprev, v = v, f * inv.to(rdt)[..., None, None]
+    return torch.linalg.eigvalsh(Tl), beta
+
+
+def chebwin_first_degree(filter_degree, max_degree):
+    """(degree of the first filter, fixed): filter_degree=None is the adaptive rule, which starts at
+    CHEBWIN_FIRST_DEGREE; an int fixes the degree of every filter.  max_degree caps both."""
+    max_degree = int(max_degree)
+    if max_degree < 1:
+        raise ValueError("chebfsi: max_degree must be >= 1, got %d" % max_degree)
+    if filter_degree is None:
+        return min(CHEBWIN_FIRST_DEGREE, max_degree), False
+    if int(filter_degree) < 1:
+        raise ValueError("chebfsi: filter_degree must be None or an int >= 1, got %r" % (filter_degree,))
+    return min(int(filter_degree), max_degree), True
+
+
+def _chebfsi_nearest(apply, orth, X, sigma, neig, w, bdims, N, dtype, rdt, max_niter, min_eps, filter_degree,
+                     max_degree, filter_tail, lanczos_steps, verbose, trace, napply):
+    """mode="nearest" of the host twin: filtered subspace iteration with the band-pass filter of
+    `chebwin_coefficients`, centred on sigma clipped to the Ritz extremes seen so far and evaluated by Clenshaw's
+    recurrence (m applies); the Ritz pairs are ordered by |lambda - sigma| and the first neig are the wanted ones;
+    after every Rayleigh-Ritz the degree rule `chebwin_degree` picks the next filter's degree.  Everything else —
+    orthonormalisation passes, guard redo, stopping rule, best-block return — is chebfsi's."""
+    import warnings
+    from xitorch_amd._util import ConvergenceWarning
+    theta, beta = _cheb_host_lanczos(apply, bdims, N, dtype, rdt, lanczos_steps)
+    emin, emax = theta.min(dim=-1)[0], theta.max(dim=-1)[0]
+    lo, hi = emin - beta, emax + beta
+    deg_now, fixed = chebwin_first_degree(filter_degree, max_degree)
+    capped = (not fixed) and deg_now == int(max_degree) and deg_now < CHEBWIN_FIRST_DEGREE
+    gbad = GUARD_BAD[rdt]
+    best_resid, best = float("inf"), None
+    history, redo, degrees = [], [], []
+    niter, passes, halved = 0, 2, False
+    eye = torch.eye(w, dtype=dtype)
+    for it in range(max_niter):
+        niter = it + 1
+        sigma_c = torch.minimum(torch.maximum(sigma, emin), emax)
+        while True:
+            coef = chebwin_coefficients(lo, hi, sigma_c, deg_now).to(rdt)              # (deg + 1, *bdims, 4)
+            Bp, Bk = None, coef[0][..., None, None, 1] * X                             # b_m = c_m X
+            for j in range(1, deg_now + 1):
+                AB = apply(Bk)
+                c4 = coef[j][..., None, None, :]
+                Bn = c4[..., 0] * AB + c4[..., 1] * Bk
+                if j > 1:
+                    Bn = Bn + c4[..., 2] * Bp
+                Bn = Bn + c4[..., 3] * X
+                Bp, Bk = Bk, Bn
+            Q = orth(Bk, passes)
+            AQ = apply(Q)
+            T = torch.matmul(_H(Q), AQ)
+            mu, Yr = torch.linalg.eigh((T + _H(T)) * 0.5)
+            sel = chebwin_select(mu, sigma)
+            lam = torch.gather(mu, -1, sel)
+            Yr = torch.gather(Yr, -1, sel.unsqueeze(-2).expand_as(Yr))
+            Xn = torch.matmul(Q, Yr)
+            R = torch.matmul(AQ, Yr[..., :neig]) - Xn[..., :neig] * lam[..., None, :neig]
+            guard = float((torch.matmul(_H(Xn), Xn) - eye).abs().max())
+            max_resid = float(R.abs().max())
+            if guard <= gbad:
+                break
+            redo.append({"iter": niter, "guard": guard, "passes": passes + 1, "degree": max(1, deg_now // 2)})
+            if len(redo) > 1:
+                raise RuntimeError("xitorch_amd chebfsi: the filtered block lost its orthonormality twice (max|X^H X - "
+                                   "I| = %.2e at iteration %d)" % (guard, niter))
+            passes, deg_now, halved = 3, max(1, deg_now // 2), True
+        X = Xn
+        degrees.append(deg_now)
+        if max_resid != max_resid:
+            max_resid = float("inf")
+        history.append(max_resid)
+        if verbose:
+            print("Iter %3d (block of %d, degree %d): resid: %.3e" % (niter, w, deg_now, max_resid))
+        if max_resid < best_resid:
+            best_resid, best = max_resid, (lam[..., :neig], Xn[..., :neig])
+        if max_resid < min_eps:
+            break
+        mu = mu.to(torch.float64)
+        emin, emax = torch.minimum(emin, mu.min(dim=-1)[0]), torch.maximum(emax, mu.max(dim=-1)[0])
+        lo, hi = torch.minimum(lo, emin), torch.maximum(hi, emax)
+        if not fixed:
+            c, e, _flat = chebwin_interval(lo, hi)
+            theta_s = chebwin_angle(torch.minimum(torch.maximum(sigma, emin), emax), c, e)
+            deg_now, capped = chebwin_degree(theta_s, chebwin_dref(lam, theta_s, c, e, neig, w), filter_tail,
+                                             max_degree)
+            if halved:
+                deg_now = max(1, deg_now // 2)
+    if best is None:
+        raise RuntimeError("xitorch_amd chebfsi: no finite residual was produced")
+    if not best_resid < min_eps:
+        warnings.warn(ConvergenceWarning("chebfsi: convergence is not achieved after %d iterations (max |resid| = %.3e "
+                                         ">= min_eps = %.3e); the best block is returned" % (niter, best_resid, min_eps)))
+    if trace is not None:
+        trace.update(niter=niter, napply=napply(), degree=degrees[-1], degrees=degrees, w=w, resid_history=history,
+                     best_resid=best_resid, sigma_centre=sigma_c.tolist(), degree_capped=bool(capped),
+                     bounds={"lo": lo.tolist(), "hi": hi.tolist(), "emin": emin.tolist(), "emax": emax.tolist()},
+                     small_eigh="library", guard_redo=redo, panel_kernel="host")
+    evals, evecs = best
+    order = torch.argsort(evals, dim=-1)                                              # ascending, like every mode
+    return torch.gather(evals, -1, order), torch.gather(evecs, -1, order.unsqueeze(-2).expand_as(evecs))
+
+
 def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguard=None, V0=None, v_init="randn",
-            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, **unused):
+            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, sigma=None,
+            filter_degree=None, max_degree=1000, filter_tail=0.1, **unused):
     """Chebyshev-filtered subspace iteration in torch ops for a Hermitian operator in HOST memory: the statement of
     `native_chebfsi.chebfsi` (same options, same refusals, same decisions).  A block of w = neig + nguard vectors; per
     outer iteration `degree` applies through the three-term filter step, two orthonormalisation passes, one apply and a
     Rayleigh-Ritz of order w; the cut of the filter follows the block's largest Ritz value.  mode="uppest" filters -A
     through the sign of the coefficients.  A block that fails the guard is redone from the pre-filter block with a third
-    pass and half the degree, which stay in force for the rest of the run; a second failure raises.  Stopping rule, best-block return and the guard thresholds are davidson's."""
+    pass and half the degree, which stay in force for the rest of the run; a second failure raises.  Stopping rule, best-block return and the guard thresholds are davidson's.
+    mode="nearest" (with sigma=, filter_degree=, max_degree=, filter_tail=) is `_chebfsi_nearest`: the same outer
+    iteration around a band-pass filter centred on sigma."""
     import warnings
     from xitorch_amd._util import ConvergenceWarning
     from xitorch_amd.linalg.native_eig import exacteig
@@ -221,10 +511,13 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     w = min(N, neig + int(nguard))
     if V0 is not None and w < V0.shape[-1]:
         w = min(N, V0.shape[-1])
+    nearest = mode == "nearest"
+    if nearest:
+        sigma = chebwin_sigma(sigma, bdims, dev)
     if N <= max(2 * w, 16):
         if trace is not None:
             trace.update(niter=0, napply=0, degree=degree, w=w, handed_to="exacteig")
-        return exacteig(A, neig, mode, None)
+        return exacteig(A, neig, mode, None, sigma=sigma) if nearest else exacteig(A, neig, mode, None)
     sign = 1.0 if mode == "lowest" else -1.0
     rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
     napply = 0
@@ -241,26 +534,14 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
 
     X = _cheb_start_block(v_init, V0, bdims, B, N, w, dtype, dev, rng_device)          # (B, w, N)
     X = orth(X.transpose(-2, -1).reshape(*bdims, N, w), 2)
+    if nearest:
+        return _chebfsi_nearest(apply, orth, X, sigma, neig, w, bdims, N, dtype, rdt, max_niter, min_eps,
+                                filter_degree, max_degree, filter_tail, lanczos_steps, verbose, trace,
+                                lambda: napply)
 
     # spectral bounds of B = sign * A from a short Lanczos run (Zhou & Li's safeguarded upper bound)
-    ks = max(2, min(int(lanczos_steps), N - 1))
-    v = _cheb_lanczos_vector(bdims, N, dtype)
-    v = v / torch.linalg.vector_norm(v, dim=-2, keepdim=True)
-    vprev = torch.zeros_like(v)
-    Tl = torch.zeros((*bdims, ks, ks), dtype=torch.float64)
-    beta = torch.zeros((*bdims,), dtype=torch.float64)
-    for j in range(ks):
-        f = apply(v)
-        al = (v.conj() * f).sum(dim=(-2, -1)).real.to(torch.float64)
-        f = f - al.to(rdt)[..., None, None] * v - beta.to(rdt)[..., None, None] * vprev
-        Tl[..., j, j] = al
-        beta = torch.linalg.vector_norm(f, dim=(-2, -1)).to(torch.float64)
-        if j + 1 < ks:
-            Tl[..., j, j + 1] = beta
-            Tl[..., j + 1, j] = beta
-            inv = torch.where(beta > 0, 1.0 / beta, torch.zeros_like(beta))
-            vprev, v = v, f * inv.to(rdt)[..., None, None]
-    theta = torch.linalg.eigvalsh(Tl) * sign                                           # Ritz values of B
+    theta, beta = _cheb_host_lanczos(apply, bdims, N, dtype, rdt, lanczos_steps)
+    theta = theta * sign                                                               # Ritz values of B
     th_min, th_max = theta.min(dim=-1)[0], theta.max(dim=-1)[0]
     b_sup = th_max + beta
     a0 = th_min
@@ -656,6 +937,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     from xitorch_amd._util import ConvergenceWarning
     from xitorch_amd.linalg.native_eig import exacteig
     calls["lobpcg"] += 1
+    refuse_nearest("lobpcg", mode)
     dev = torch.device(A.device)
     if dev.type != "cpu":
         raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "

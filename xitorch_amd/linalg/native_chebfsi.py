@@ -18,6 +18,12 @@ Storage: the Ritz block, the two ring panels, the product panel, the best block 
 a short Lanczos run on the device (`xk_kry_dots` + `xk_cheb_step` as its three-term update).  `host_eig.chebfsi` is the
 same algorithm in torch ops for operators in host memory.  Not built: an overlap operator M, batch sharding, locking of
 converged columns.
+
+`mode="nearest"` with `sigma=` (`_nearest`; Li, Xi, Vecharynski, Yang, Saad, SIAM J. Sci. Comput. 38 (2016) A2512) runs
+the same outer iteration around a Jackson-damped Chebyshev band-pass centred on sigma: the filter is evaluated by
+Clenshaw's recurrence, one `xk_cheb_clenshaw` between two applies, on the same five panels (the pre-filter block is the
+X0 of every step: no accumulator panel); the Ritz pairs are ordered by |lambda - sigma| on the device; the degree of the
+next filter is chosen from the block's Ritz values (one more host read per outer iteration).  DESIGN.md section 3.14.
 """
 import warnings
 from types import SimpleNamespace
@@ -28,18 +34,25 @@ from xitorch_amd.linalg._panel import PanelOperator, pad_len, batch_count, real_
 from xitorch_amd.linalg._block import block_ops, native_partial_eigh, GUARD_BAD
 from xitorch_amd.linalg.native_krylov import _Kry
 from xitorch_amd.linalg import host_eig
-from xitorch_amd.linalg.host_eig import cheb_coefficients, cheb_default_nguard
+from xitorch_amd.linalg.host_eig import (cheb_coefficients, cheb_default_nguard, chebwin_coefficients, chebwin_select,
+                                         chebwin_sigma, chebwin_first_degree, chebwin_interval, chebwin_angle,
+                                         chebwin_degree, chebwin_dref, CHEBWIN_FIRST_DEGREE)
 
 __all__ = ["chebfsi"]
 
 
-def _rayleigh_ritz(ops, Q, AQ, X, scratch, hstatus, neig, sign):
-    """X <- the Ritz block of span(Q) ordered by sign * lambda ascending; returns (lam (Bt, w) true eigenvalues in
-    that order, mu = sign * lam (ascending), [max|resid| over the wanted columns, Cholesky flag, guard])"""
+def _rayleigh_ritz(ops, Q, AQ, X, scratch, hstatus, neig, sign, sigma=None):
+    """X <- the Ritz block of span(Q) ordered by sign * lambda ascending — with `sigma` (Bt,) (mode="nearest", sign =
+    1) by |lambda - sigma| ascending, a permutation of the small device tensors; returns (lam (Bt, w) true eigenvalues
+    in that order, mu = sign * lam (ascending), [max|resid| over the wanted columns, Cholesky flag, guard])"""
     w = ops.w
     T = ops.rr_matrix(Q, AQ, sign)                                       # T[b, i, c] = sign <Q_i, (A Q)_c>
     mu, Y = ops.eigh_lowest(T, w, w)                                     # (Bt, w), (Bt, w, w) = [basis index, pair]
     lam = (mu * sign).contiguous()
+    if sigma is not None:
+        sel = chebwin_select(lam, sigma)
+        lam = torch.gather(lam, -1, sel).contiguous()
+        Y = torch.gather(Y, -1, sel.unsqueeze(-2).expand_as(Y)).contiguous()
     if hstatus is None:
         ops.rmax.zero_()
         K.ritz_residual(Q, AQ, Y, lam, X, scratch, ops.rmax, w, neig)
@@ -97,8 +110,92 @@ def _lanczos_bounds(op, Bt, N, dtype, device, bdims, steps, sign):
     return theta, beta
 
 
+def _nearest(ops, op, hstatus, orth, panels, Tn, theta, fnorm, sigma, neig, w, N, bdims, rdt, max_niter, min_eps,
+             filter_degree, max_degree, filter_tail, verbose, trace):
+    """mode="nearest" on the five panels of `chebfsi`: see `host_eig._chebfsi_nearest`, whose decisions these are.  Per
+    filter of degree m: b_m = c_m X by one `xk_cheb_step`, then m times [apply, `xk_cheb_clenshaw`] on a ring of two
+    panels with the pre-filter block X as the X0 of every step; the coefficient table and the degree rule are torch ops
+    on (Bt,) device tensors."""
+    X, R0, R1, AY, best_X = panels
+    theta = theta.to(torch.float64)
+    emin, emax = theta.min(dim=-1)[0], theta.max(dim=-1)[0]
+    lo, hi = emin - fnorm, emax + fnorm
+    deg_now, fixed = chebwin_first_degree(filter_degree, max_degree)
+    capped = (not fixed) and deg_now == int(max_degree) and deg_now < CHEBWIN_FIRST_DEGREE
+    gbad = GUARD_BAD[rdt]
+    best_resid, best_lam = float("inf"), None
+    history, redo, degrees = [], [], []
+    niter, passes, halved = 0, 2, False
+    for it in range(max_niter):
+        niter = it + 1
+        sigma_c = torch.minimum(torch.maximum(sigma, emin), emax)
+        while True:
+            coef = chebwin_coefficients(lo, hi, sigma_c, deg_now).contiguous()           # (degree + 1, Bt, 4)
+            # ring: b_{k+2} is overwritten by b_k; the pre-filter block X is the X0 of every step and is kept
+            K.cheb_step(X, X, R0, coef[0, :, :3].contiguous(), out=R0, N=N)              # b_m = c_m X (R0 is not read)
+            Yp, Y = R1, R0
+            for j in range(1, deg_now + 1):
+                op.apply(Y, AY)
+                K.cheb_clenshaw(AY, Y, Yp, X, coef[j], N=N)                              # row 1: gamma = 0, Yp not read
+                Yp, Y = Y, Yp
+            Q, other = Y, Yp                                                             # p(A) X, and b_1 (dead)
+            orth(Q, passes)
+            op.apply(Q, AY)
+            lam, _mu, (max_resid, chol_flag, guard) = _rayleigh_ritz(ops, Q, AY, other, Tn, hstatus, neig, 1.0, sigma)
+            if guard != guard:
+                guard = float("inf")
+            if chol_flag == 0 and guard <= gbad:
+                break
+            redo.append({"iter": niter, "guard": guard, "chol_flag": chol_flag, "passes": 3,
+                         "degree": max(1, deg_now // 2)})
+            if len(redo) > 1:
+                raise RuntimeError("xitorch_amd chebfsi: the filtered block lost its orthonormality twice (max|X^H X - "
+                                   "I| = %.2e, Cholesky flag %d, at iteration %d)" % (guard, int(chol_flag), niter))
+            passes, deg_now, halved = 3, max(1, deg_now // 2), True
+        # the new Ritz block lives in `other`: it becomes X; the old X and Q are the ring of the next filter
+        X, R0, R1 = other, X, Q
+        degrees.append(deg_now)
+        if max_resid != max_resid:
+            max_resid = float("inf")
+        history.append(max_resid)
+        if verbose:
+            print("Iter %3d (block of %d, degree %d): resid: %.3e" % (niter, w, deg_now, max_resid))
+        if max_resid < best_resid:
+            best_resid, best_lam = max_resid, lam[:, :neig]
+            best_X.copy_(X)
+        if max_resid < min_eps:
+            break
+        lam64 = lam.to(torch.float64)
+        emin, emax = torch.minimum(emin, lam64.min(dim=-1)[0]), torch.maximum(emax, lam64.max(dim=-1)[0])
+        lo, hi = torch.minimum(lo, emin), torch.maximum(hi, emax)
+        if not fixed:
+            c, e, _flat = chebwin_interval(lo, hi)
+            theta_s = chebwin_angle(torch.minimum(torch.maximum(sigma, emin), emax), c, e)
+            deg_now, capped = chebwin_degree(theta_s, chebwin_dref(lam64, theta_s, c, e, neig, w), filter_tail,
+                                             max_degree)                                 # the one extra host read
+            if halved:
+                deg_now = max(1, deg_now // 2)
+    if best_lam is None:
+        raise RuntimeError("xitorch_amd chebfsi: no finite residual was produced")
+    if not best_resid < min_eps:
+        warnings.warn(ConvergenceWarning("chebfsi: convergence is not achieved after %d iterations (max |resid| = %.3e "
+                                         ">= min_eps = %.3e); the best block is returned" % (niter, best_resid, min_eps)))
+    if trace is not None:
+        trace.update(niter=niter, napply=op.napply, degree=degrees[-1], degrees=degrees, w=w, resid_history=history,
+                     best_resid=best_resid, sigma_centre=sigma_c.reshape(tuple(bdims)).tolist(), degree_capped=bool(capped),
+                     bounds={k: v.reshape(tuple(bdims)).tolist() for k, v in (("lo", lo), ("hi", hi), ("emin", emin),
+                                                                        ("emax", emax))},
+                     small_eigh=ops.small_eigh, guard_redo=redo,
+                     panel_kernel=op.last_kernel if op.kind != "generic" else "generic")
+    order = torch.argsort(best_lam, dim=-1)                                              # ascending, like every mode
+    evals = torch.gather(best_lam, -1, order).reshape(*bdims, neig)
+    evecs = ops.result(best_X, neig, bdims)
+    return evals, torch.gather(evecs, -1, order.reshape(*bdims, 1, neig).expand_as(evecs))
+
+
 def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguard=None, V0=None, v_init="randn",
-            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, **unused):
+            rng_device="cpu", lanczos_steps=12, verbose=False, trace=None, process_group=None, sigma=None,
+            filter_degree=None, max_degree=1000, filter_tail=0.1, **unused):
     """
     Chebyshev-filtered subspace iteration for the ``neig`` lowest / uppermost eigenpairs of a large Hermitian operator
     (dense, banded, CSR or a user ``_mv``; float64, float32, complex128, complex64; any batch shape), on the HIP kernels.
@@ -112,7 +209,19 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
         Stop when the largest residual element ``max|A X - X diag(lam)|`` over the wanted columns of all operators is
         below this (davidson's rule); otherwise the best block seen is returned with a ``ConvergenceWarning``
     degree: int
-        Degree of the Chebyshev filter
+        Degree of the Chebyshev filter (``"lowest"`` / ``"uppest"``; not used by ``"nearest"``)
+    sigma: number or real tensor broadcastable to the batch dimensions
+        ``mode="nearest"``: the ``neig`` pairs nearest ``sigma`` (no gradient flows to it).  The filter is the
+        Jackson-damped Chebyshev expansion of a delta function (Li, Xi, Vecharynski, Yang, Saad, SISC 2016), centred on
+        ``sigma`` clipped to the Ritz extremes seen so far and evaluated by Clenshaw's recurrence: per filter ``m``
+        applies and ``m`` streaming passes (one ``xk_cheb_step``, ``m`` ``xk_cheb_clenshaw``), no accumulator panel
+    filter_degree: int or None
+        ``mode="nearest"``: ``None`` = the first filter has degree 20 and after every Rayleigh-Ritz the smallest degree
+        of the ladder 8, 11, 14, 18, ... whose filter has fallen to ``filter_tail`` at the angular distance of the
+        ``(neig + ceil(nguard / 2))``-th nearest Ritz value is taken (one more host read per outer iteration, of that
+        integer); an int fixes the degree
+    max_degree, filter_tail: int, float
+        ``mode="nearest"``: the cap of the ladder (reported in ``trace["degree_capped"]``) and the tail level
     nguard: int or None
         Guard vectors: the block has ``neig + nguard`` columns.  Default ``max(8, ceil(neig / 4))``, capped at the order
     V0: tensor or None
@@ -123,7 +232,8 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
         Steps of the Lanczos run that estimates the spectral bounds (upper bound ``theta_max + |f_k|``)
     trace: dict or None
         Receives ``niter``, ``napply``, ``degree``, ``w``, ``bounds``, ``small_eigh`` (``"native"`` / ``"library"``),
-        ``guard_redo``, ``panel_kernel``, ``resid_history``
+        ``guard_redo``, ``panel_kernel``, ``resid_history``; ``mode="nearest"`` adds ``degrees`` (per outer
+        iteration), ``sigma_centre``, ``degree_capped`` and ``bounds`` = ``lo, hi, emin, emax``
 
     ``M`` and ``process_group`` raise ``NotImplementedError``.  ``mode="uppest"`` filters ``-A`` by negating the
     coefficients.  A block wide enough to span (half of) the space is handed to ``exacteig``.  A block that fails the
@@ -137,7 +247,8 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
         # device dispatch (see native_eig.davidson): an operator in HOST memory is served by host_eig.py
         return host_eig.chebfsi(A, neig, mode, M, max_niter=max_niter, min_eps=min_eps, degree=degree, nguard=nguard,
                                 V0=V0, v_init=v_init, rng_device=rng_device, lanczos_steps=lanczos_steps,
-                                verbose=verbose, trace=trace, process_group=process_group)
+                                verbose=verbose, trace=trace, process_group=process_group, sigma=sigma,
+                                filter_degree=filter_degree, max_degree=max_degree, filter_tail=filter_tail)
     host_eig._cheb_check_args("chebfsi", M, process_group)
     require_hip(A, "chebfsi")
     dtype = A.dtype
@@ -149,11 +260,14 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
     w = min(N, neig + int(nguard))
     if V0 is not None and w < V0.shape[-1]:
         w = min(N, V0.shape[-1])
+    nearest = mode == "nearest"
+    if nearest:
+        sigma = chebwin_sigma(sigma, bdims, device)
     if N <= max(2 * w, 16):
         if trace is not None:
             trace.update(niter=0, napply=0, degree=degree, w=w, handed_to="exacteig")
-        return exacteig(A, neig, mode, None)
-    sign = 1.0 if mode == "lowest" else -1.0
+        return exacteig(A, neig, mode, None, sigma=sigma) if nearest else exacteig(A, neig, mode, None)
+    sign = 1.0 if mode == "lowest" or nearest else -1.0
     rdt = real_dtype(dtype)
     ops = block_ops(Bt, N, w, dtype, device, wide=True)
     hstatus = torch.zeros((Bt + 1,), dtype=torch.float64, device=device) if dtype.is_complex else None   # xk_herm_ritz
@@ -175,6 +289,9 @@ def chebfsi(A, neig, mode, M=None, max_niter=100, min_eps=1e-6, degree=12, nguar
 
     ks = max(2, min(int(lanczos_steps), N - 1))
     theta, fnorm = _lanczos_bounds(op, Bt, N, dtype, device, bdims, ks, sign)
+    if nearest:
+        return _nearest(ops, op, hstatus, orth, (X, R0, R1, AY, best_X), Tn, theta, fnorm, sigma.reshape(Bt), neig, w, N,
+                        bdims, rdt, max_niter, min_eps, filter_degree, max_degree, filter_tail, verbose, trace)
     b_sup = theta.max(dim=-1)[0].to(torch.float64) + fnorm
     a0 = theta.min(dim=-1)[0].to(torch.float64)
     a = theta.to(torch.float64).median(dim=-1)[0]

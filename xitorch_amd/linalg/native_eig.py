@@ -520,6 +520,8 @@ def davidson(A, neig, mode, M=None, max_niter=1000, nguess=None, v_init="randn",
     a-posteriori guard: a run whose Ritz blocks fail it and that cannot be rolled back (thick restarts rewrite the
     basis) is repeated once from the start block with three re-orthogonalised projection passes; a second failure
     raises — a block that fails the guard is never returned."""
+    from xitorch_amd.linalg.host_eig import refuse_nearest
+    refuse_nearest("davidson", mode)
     kw = dict(M=M, max_niter=max_niter, nguess=nguess, v_init=v_init, max_addition=max_addition, min_eps=min_eps,
               verbose=verbose, V0=V0, process_group=process_group, trace=trace, rng_device=rng_device,
               small_eigh=small_eigh, overlap=overlap, precond=precond, reserve_cus=reserve_cus, restart=restart,
@@ -1047,28 +1049,32 @@ class _NativeEigh(torch.autograd.Function):
         return _degen_eigh_backward(lam_all, U, gl, gU), None, None
 
 
-def exacteig(A, neig, mode, M=None):
+def exacteig(A, neig, mode, M=None, sigma=None):
     """Eigendecomposition by building the full matrix (reference: exacteig, symeig.py:11-44).  On a HIP device, for real
     matrices of order 8 .. 1536 and up to 256 wanted pairs — the reference's own benchmark shapes, n in {100, 350, 700} with
     neig = 10 (benchmarks/benchmarks_solve.py:37-59) — the eigenpairs come from the native dense eigensolver
     (`native_partial_eigh`: only the wanted pairs are computed); everything else (CPU tensors, complex Hermitian, larger
-    orders) is `torch.linalg.eigh` like the reference.  Both carry the degeneracy-aware backward of degen_symeig."""
+    orders) is `torch.linalg.eigh` like the reference.  Both carry the degeneracy-aware backward of degen_symeig.
+    mode="nearest" (extension) takes the full `eigh` and gathers the `neig` pairs nearest `sigma`, ascending."""
+    nearest = mode == "nearest"
+    if nearest and sigma is None:
+        raise ValueError("exacteig: mode='nearest' needs the target: pass sigma=")
     Amat = A.fullmatrix()
     if M is None:
-        if _native_dense_ok(Amat, neig):
+        if not nearest and _native_dense_ok(Amat, neig):
             return _NativeEigh.apply(Amat, neig, mode)
         evals, evecs = _DegenEigh.apply(Amat)
-        return take_eigpairs(evals, evecs, neig, mode)
+        return take_eigpairs(evals, evecs, neig, mode, sigma)
     L = torch.linalg.cholesky(M.fullmatrix())
     Linv = torch.inverse(L)
     LinvH = Linv.transpose(-2, -1).conj()
     A2 = torch.matmul(Linv, torch.matmul(Amat, LinvH))
-    if _native_dense_ok(A2, neig):
+    if not nearest and _native_dense_ok(A2, neig):
         A2 = (A2 + A2.transpose(-2, -1)) * 0.5          # (the kernels read one triangle: make both agree)
         evals, evecs = _NativeEigh.apply(A2, neig, mode)
     else:
         evals, evecs = _DegenEigh.apply(A2)
-        evals, evecs = take_eigpairs(evals, evecs, neig, mode)
+        evals, evecs = take_eigpairs(evals, evecs, neig, mode, sigma)
     return evals, torch.matmul(LinvH, evecs)
 
 

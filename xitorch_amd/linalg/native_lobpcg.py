@@ -129,6 +129,7 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     Not built: locking / deflation of converged columns, batch sharding, an MFMA form of the rotation.
     """
     from xitorch_amd.linalg.native_eig import exacteig
+    host_eig.refuse_nearest("lobpcg", mode)
     device = torch.device(A.device)
     if device.type == "cpu":
         # device dispatch (see native_eig.davidson): an operator in HOST memory is served by host_eig.py

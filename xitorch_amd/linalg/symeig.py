@@ -38,7 +38,16 @@ def symeig(A, neig=None, mode="lowest", M=None, bck_options={}, method=None, **f
     neig: int or None
         Number of eigenpairs (``None``: all)
     mode: str
-        ``"lowest"`` or ``"uppermost"``/``"uppest"``
+        ``"lowest"``, ``"uppermost"``/``"uppest"``, or ``"nearest"`` (extension): the ``neig`` pairs whose eigenvalues
+        are nearest the target ``sigma=`` (a forward option: a number, or a real tensor broadcastable to the batch
+        dimensions; it carries no gradient).  Served by ``method="exacteig"`` (full ``eigh``, then the selection) and
+        ``method="chebfsi"`` (a Jackson-damped Chebyshev band-pass filter centred on ``sigma``, ``M=None``; options
+        ``filter_degree`` (``None``: adaptive), ``max_degree`` (1000), ``filter_tail`` (0.1)); ``"davidson"`` and
+        ``"lobpcg"`` raise ``NotImplementedError``.  A ``sigma`` outside the spectrum gives the ``"lowest"`` /
+        ``"uppest"`` pairs.  A ``sigma`` deep inside a spectral gap (its distance to the nearest eigenvalue far
+        exceeds the spread of the wanted ones) converges slowly with ``chebfsi``: no filter centred on ``sigma`` then
+        separates the ``neig``-th from the next eigenvalue well.  An exact tie in ``|lambda - sigma|`` at the boundary
+        of the wanted set makes the answer ambiguous.  Missing ``sigma`` raises ``ValueError``.
     M: LinearOperator or None
         Hermitian right-hand-side operator ``(*BM, q, q)`` (``None``: identity)
     bck_options: dict
@@ -81,8 +90,12 @@ def symeig(A, neig=None, mode="lowest", M=None, bck_options={}, method=None, **f
         A.check()
         if M is not None:
             M.check()
+    if mode == "nearest" and fwd_options.get("sigma") is None:
+        raise ValueError("symeig: mode='nearest' needs the target: pass sigma= (a number, or a real tensor "
+                         "broadcastable to the batch dimensions)")
     if method == "exacteig":
-        return exacteig(A, neig, mode, M)
+        return exacteig(A, neig, mode, M, sigma=fwd_options.get("sigma")) if mode == "nearest" \
+            else exacteig(A, neig, mode, M)
     fwd_options["method"] = method
     params = A.getlinopparams()
     mparams = M.getlinopparams() if M is not None else []
@@ -191,7 +204,7 @@ def _svd_gkl(A, k, mode, bck_options, fwd_options):
 
 
 def _custom_exacteig(A, neig, mode, M=None, **options):
-    return exacteig(A, neig, mode, M)
+    return exacteig(A, neig, mode, M, sigma=options.get("sigma"))
 
 
 _SYMEIG_METHODS = {"davidson": davidson, "chebfsi": chebfsi, "lobpcg": lobpcg, "custom_exacteig": _custom_exacteig}
