@@ -892,6 +892,55 @@ int xk_lsmr_update_c64(const float* vh, float* h, float* hbar, float* x, const f
                        double* state, float* run, int S, int N, long ld, int nblk, int nblk_u, int k, double damp,
                        double atol, double btol, double conlim, void* stream);
 
+/* ---- stochastic Lanczos quadrature (xk_slq.hip; extension, no reference counterpart): z^H f(A) z of a Hermitian
+ * operator by Gauss quadrature on the Lanczos tridiagonal.  Vectors are (S, ld) arrays as above (_c128 / _c64:
+ * interleaved complex, N and ld in complex elements); Pb and Pa are the partials xk_kry_dots writes ((S, 64) real, or
+ * (S, 64, 2) (re, im) pairs for the complex types, of which the real part is used), Pin / Pout are (S, 64) REAL
+ * partials of |y|^2.  The per-system scalars are DOUBLES whatever the vector type: state is (2, S, xk_slq_state_len())
+ * doubles, step k reads slot k & 1 and writes slot (k + 1) & 1.  Entry i of a slot: 0 beta (norm of the Lanczos vector
+ * of the last step; after init |z|), 1 the norm before it (0: none), 2 flag (0 running, 1 frozen by a breakdown, 2
+ * z = 0), 3 m (steps recorded), 4 tnorm (running maximum row sum of the Jacobi matrix), 5 the last row's sum short of
+ * its next beta, 6 |z|^2, 7 the last alpha.  Tal, Tbe: (S, nsteps) doubles; the Jacobi matrix of system s is
+ * diag(Tal[s, 0 .. m)) with the off-diagonal Tbe[s, 1 .. m) (Tbe[s, 0] = |z|).
+ * xk_slq_init: beta_1 = sqrt(sum Pb); r2 <- z; the start state into slot k & 1 (z = 0: flag 2).
+ * xk_slq_step: beta = sqrt(sum Pin) (first step: the state's); beta <= 64 eps tnorm (eps: machine epsilon of the
+ *   vector type): the system is frozen (flag 1) and nothing else of it is written, now or later; else alpha =
+ *   sum Pa / beta^2, r1 <- W / beta - (alpha / beta) r2 - (beta / oldb) r1 (first step: r1 is not read), Pout <- the
+ *   nblk block partials of |r1|^2, Tal[s, m] <- alpha, Tbe[s, m] <- beta, m + 1 and the rest into slot (k + 1) & 1.
+ *   The caller swaps r1 and r2, and Pin and Pout.
+ * xk_slq_quad (double, whatever the vector type): for every system the eigenvalues theta[s, 0 .. m) and the squared
+ *   first eigenvector components weight[s, 0 .. m) of its Jacobi matrix (implicit QL; entries [m, nsteps) are set to
+ *   0), out[s] = |z|^2 sum_k weight f(theta) with fn 0 log, 1 1/x, 2 sqrt, 3 1/sqrt, 4 exp(param x), 5 x, and flag[s]:
+ *   bit 0 a node <= 0 under fn 0 .. 3, bit 1 the QL iteration did not converge; a flagged system's out is NaN.
+ *   m and |z|^2 are read from slot k & 1.
+ * XK_ERR_ARG, nothing launched: N <= 0 or beyond 2^31 - 1 real elements (complex: 2 N), S < 0, k < 0, nblk outside
+ *   1 .. 64, ld below N rounded up to the 16 B vector, a NULL pointer, aliased arrays, nsteps outside 1 .. 128, an
+ *   unknown fn.  XK_ERR_UNSUPPORTED, nothing launched: a
+ *   vector pointer or a pitch that is not 16 B aligned.  S = 0 returns 0 and launches nothing. */
+int xk_slq_state_len(void);
+int xk_slq_init_f64(const double* z, double* r2, const double* Pb, double* state, int S, int N, long ld, int nblk, int k,
+                    void* stream);
+int xk_slq_step_f64(const double* W, const double* r2, double* r1, const double* Pa, const double* Pin, double* Pout,
+                    double* state, double* Tal, double* Tbe, int S, int N, long ld, int nblk, int nsteps, int k,
+                    void* stream);
+int xk_slq_init_f32(const float* z, float* r2, const float* Pb, double* state, int S, int N, long ld, int nblk, int k,
+                    void* stream);
+int xk_slq_step_f32(const float* W, const float* r2, float* r1, const float* Pa, const float* Pin, float* Pout,
+                    double* state, double* Tal, double* Tbe, int S, int N, long ld, int nblk, int nsteps, int k,
+                    void* stream);
+int xk_slq_init_c128(const double* z, double* r2, const double* Pb, double* state, int S, int N, long ld, int nblk, int k,
+                     void* stream);
+int xk_slq_step_c128(const double* W, const double* r2, double* r1, const double* Pa, const double* Pin, double* Pout,
+                     double* state, double* Tal, double* Tbe, int S, int N, long ld, int nblk, int nsteps, int k,
+                     void* stream);
+int xk_slq_init_c64(const float* z, float* r2, const float* Pb, double* state, int S, int N, long ld, int nblk, int k,
+                    void* stream);
+int xk_slq_step_c64(const float* W, const float* r2, float* r1, const float* Pa, const float* Pin, float* Pout,
+                    double* state, double* Tal, double* Tbe, int S, int N, long ld, int nblk, int nsteps, int k,
+                    void* stream);
+int xk_slq_quad(const double* Tal, const double* Tbe, const double* state, double* theta, double* weight, double* out,
+                int* flag, int S, int nsteps, int k, int fn, double param, void* stream);
+
 /* ---- device-side collectives of the sharded solvers (RCCL over xGMI) -------------------------
  * The per-iteration exchanges that reproduce the reference's GLOBAL decisions under batch sharding — MAX of
  * {max|resid|, flags} (xitorch/_impls/linalg/symeig.py:188-203), MAX of {max residual norm, unconverged flag}

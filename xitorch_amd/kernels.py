@@ -671,6 +671,46 @@ def lsmr_update(vh, h, hbar, x, Pu, Pv, Pxin, Pxout, state, run, S, N, ld, nblk,
                 float(conlim), raw=raw)
 
 
+# --------------------------------------------------------------------------- Lanczos quadrature (xk_slq.hip)
+SLQ_MAX_STEPS = 128                      # the projected matrix of xk_slq_quad lives on chip
+SLQ_FN = {"log": 0, "inv": 1, "sqrt": 2, "invsqrt": 3, "exp": 4, "identity": 5}
+
+
+def slq_state(S, device):
+    """zeroed per-system scalar state of the quadrature kernels: (2 slots, S, xk_slq_state_len()) doubles"""
+    return torch.zeros((2, S, fn("xk_slq_state_len")()), dtype=torch.float64, device=device)
+
+
+def slq_init(z, r2, Pb, state, S, N, ld, nblk, k, raw=False):
+    """beta_1 = sqrt(<z, z>) from the xk_kry_dots partials Pb, r2 <- z, the start state in slot k & 1"""
+    require_device(r2, "vector")
+    return call("xk_slq_init", r2.dtype, ptr(z), ptr(r2), ptr(Pb), ptr(state), S, N, ld, nblk, int(k), raw=raw)
+
+
+def slq_step(W, r2, r1, Pa, Pin, Pout, state, Tal, Tbe, S, N, ld, nblk, nsteps, k, raw=False):
+    """Lanczos step k on un-normalised vectors: alpha from the xk_kry_dots partials Pa of <r2, W>, beta from the
+    partials Pin of the step before; r1 <- W / beta - (alpha / beta) r2 - (beta / oldb) r1, Pout <- |r1|^2 partials,
+    alpha and beta into Tal, Tbe, state slot (k + 1) & 1.  The caller swaps r1 and r2, Pin and Pout."""
+    require_device(r1, "vector")
+    return call("xk_slq_step", r1.dtype, ptr(W), ptr(r2), ptr(r1), ptr(Pa), ptr(Pin), ptr(Pout), ptr(state), ptr(Tal),
+                ptr(Tbe), S, N, ld, nblk, int(nsteps), int(k), raw=raw)
+
+
+def slq_quad(Tal, Tbe, state, k, fn_code=0, param=0.0, raw=False):
+    """Gauss quadrature of every system's Jacobi matrix (m and |z|^2 from state slot k & 1) ->
+    (theta (S, nsteps), weight (S, nsteps), out (S,) = |z|^2 sum weight f(theta), flag (S,) int32).  fn_code: SLQ_FN."""
+    require_device(Tal, "Lanczos coefficients")
+    S, nsteps = Tal.shape
+    theta, weight = torch.empty_like(Tal), torch.empty_like(Tal)
+    out = torch.empty((S,), dtype=torch.float64, device=Tal.device)
+    flag = torch.empty((S,), dtype=torch.int32, device=Tal.device)
+    rc = call("xk_slq_quad", None, ptr(Tal), ptr(Tbe), ptr(state), ptr(theta), ptr(weight), ptr(out), ptr(flag), S,
+              nsteps, int(k), int(fn_code), float(param), raw=raw)
+    if raw:
+        return rc
+    return theta, weight, out, flag
+
+
 # --------------------------------------------------------------------------- Chebyshev filter step (xk_cheb.hip)
 def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
     """out[b,c,:N] = coef[b,0] * AY[b,c,:N] + coef[b,1] * Y[b,c,:N] + coef[b,2] * Yprev[b,c,:N]  (xk_cheb_step_*): the
