@@ -941,6 +941,46 @@ int xk_slq_step_c64(const float* W, const float* r2, float* r1, const float* Pa,
 int xk_slq_quad(const double* Tal, const double* Tbe, const double* state, double* theta, double* weight, double* out,
                 int* flag, int S, int nsteps, int k, int fn, double param, void* stream);
 
+/* ---- f(A) B by two-pass Lanczos (xk_fnm.hip; extension, no reference counterpart).  Pass 1 is the xk_slq_init /
+ * xk_slq_step run above on the start vectors b; the entry points here turn its Tal, Tbe and state into the coefficients
+ * of f(A) b in the Lanczos basis and replay the recurrence to accumulate X = sum_k (c_k / beta_k) r2_k without a stored
+ * basis.  Vectors, pitches, Tal, Tbe and state are laid out as in the xk_slq block.
+ * xk_fnm_eig (double, whatever the vector type): for every system the eigenvalues theta[s, 0 .. m) and the eigenvector
+ *   matrix of its Jacobi matrix by implicit QL with the rotations accumulated: Qt (S, nsteps, nsteps) doubles,
+ *   COLUMN-major: Qt[s, k, j] is component j of the eigenvector of theta[s, k].  Entries at and beyond m are set to 0.
+ *   flag[s] (int): 2 when QL did not converge within the sweep cap of xk_slq_quad, else 0.  m is read from slot k & 1.
+ * xk_fnm_coeff: C[s, j] = |b_s| sum_k Qt[s, k, j] f_k Qt[s, k, 0], k ascending, for j < m; 0 for j >= m.  fn 0 .. 5:
+ *   f_k = the named function of xk_slq_quad at theta[s, k] (param: fn 4); a node <= 0 under fn 0 .. 3 sets bit 0 of
+ *   flag[s].  fn = -1: f_k = fvals[s, k], the caller's values of the function at theta ((S, nsteps) doubles; cplx != 0:
+ *   (S, nsteps, 2) (re, im) pairs).  C is (S, nsteps) doubles, or (S, nsteps, 2) pairs when cplx != 0 (a named function
+ *   has imaginary part 0).  flag[s] must hold what xk_fnm_eig wrote; a flagged system's C[s, 0 .. m) is NaN.
+ *   tail[s] = |C[s, m-4 .. m)| / |C[s, 0 .. m)| in the 2-norm, 0 when m <= 4.  m and |b|^2 are read from slot k & 1.
+ * xk_fnm_step: step k of pass 2 for every system with k < m (m and the flag from slot kstate & 1) whose flag is not 2:
+ *   X += (C[s, k] / Tbe[s, k]) r2 (_c128 / _c64: C holds (re, im) pairs); then, unless `last` != 0 or k + 1 = m,
+ *   r1 <- (W c0 - c2 r2) - c1 r1 with c0 = 1 / beta, c2 = alpha / beta, c1 = beta / Tbe[s, k - 1] formed from
+ *   alpha = Tal[s, k], beta = Tbe[s, k] exactly as xk_slq_step forms them, so that r1 is the vector pass 1 wrote, bit
+ *   for bit (k = 0: no r1 term, r1 is not read).  The caller swaps r1 and r2.  W == NULL means last; r1 may then be
+ *   NULL too.  Every other system is left untouched.
+ * XK_ERR_ARG / XK_ERR_UNSUPPORTED: as in the xk_slq block; also k >= nsteps or kstate < 0 (xk_fnm_step), fn outside
+ *   -1 .. 5 or fn = -1 without fvals (xk_fnm_coeff).  XK_ERR_UNSUPPORTED also when xk_slq_state_len() is not the state
+ *   length these entry points were written for. */
+int xk_fnm_eig(const double* Tal, const double* Tbe, const double* state, double* theta, double* Qt, int* flag, int S,
+               int nsteps, int k, void* stream);
+int xk_fnm_coeff(const double* Qt, const double* theta, const double* state, const double* fvals, double* C,
+                 double* tail, int* flag, int S, int nsteps, int k, int fn, double param, int cplx, void* stream);
+int xk_fnm_step_f64(const double* W, const double* r2, double* r1, double* X, const double* C, const double* Tal,
+                    const double* Tbe, const double* state, int S, int N, long ld, int nblk, int nsteps, int k,
+                    int kstate, int last, void* stream);
+int xk_fnm_step_f32(const float* W, const float* r2, float* r1, float* X, const double* C, const double* Tal,
+                    const double* Tbe, const double* state, int S, int N, long ld, int nblk, int nsteps, int k,
+                    int kstate, int last, void* stream);
+int xk_fnm_step_c128(const double* W, const double* r2, double* r1, double* X, const double* C, const double* Tal,
+                     const double* Tbe, const double* state, int S, int N, long ld, int nblk, int nsteps, int k,
+                     int kstate, int last, void* stream);
+int xk_fnm_step_c64(const float* W, const float* r2, float* r1, float* X, const double* C, const double* Tal,
+                    const double* Tbe, const double* state, int S, int N, long ld, int nblk, int nsteps, int k,
+                    int kstate, int last, void* stream);
+
 /* ---- device-side collectives of the sharded solvers (RCCL over xGMI) -------------------------
  * The per-iteration exchanges that reproduce the reference's GLOBAL decisions under batch sharding — MAX of
  * {max|resid|, flags} (xitorch/_impls/linalg/symeig.py:188-203), MAX of {max residual norm, unconverged flag}

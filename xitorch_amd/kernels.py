@@ -711,6 +711,52 @@ def slq_quad(Tal, Tbe, state, k, fn_code=0, param=0.0, raw=False):
     return theta, weight, out, flag
 
 
+# --------------------------------------------------------------------------- f(A) B by two-pass Lanczos (xk_fnm.hip)
+def fnm_eig(Tal, Tbe, state, k, raw=False):
+    """eigenvalues and the whole eigenvector matrix of every system's Jacobi matrix (m from state slot k & 1) ->
+    (theta (S, nsteps), Qt (S, nsteps, nsteps) column-major: Qt[s, i] is the eigenvector of theta[s, i], flag (S,)
+    int32: 2 where QL did not converge)"""
+    require_device(Tal, "Lanczos coefficients")
+    S, nsteps = Tal.shape
+    theta = torch.empty_like(Tal)
+    Qt = torch.empty((S, nsteps, nsteps), dtype=torch.float64, device=Tal.device)
+    flag = torch.empty((S,), dtype=torch.int32, device=Tal.device)
+    rc = call("xk_fnm_eig", None, ptr(Tal), ptr(Tbe), ptr(state), ptr(theta), ptr(Qt), ptr(flag), S, nsteps, int(k),
+              raw=raw)
+    if raw:
+        return rc
+    return theta, Qt, flag
+
+
+def fnm_coeff(Qt, theta, state, flag, k, fn_code=-1, param=0.0, fvals=None, cplx=False, raw=False):
+    """C[s, j] = |b_s| sum_i Qt[s, i, j] f_i Qt[s, i, 0] -> (C (S, nsteps) float64, or (S, nsteps, 2) (re, im) pairs
+    with cplx; tail (S,)).  fn_code: SLQ_FN (bit 0 of `flag` is set for a node <= 0 under a positivity function), or -1
+    with fvals (S, nsteps) float64 / (S, nsteps, 2) pairs: the function already applied to theta.  `flag` is updated
+    in place."""
+    require_device(Qt, "eigenvectors")
+    S, nsteps = theta.shape
+    if fvals is not None and (fvals.dtype != torch.float64 or not fvals.is_contiguous()
+                              or tuple(fvals.shape) != ((S, nsteps, 2) if cplx else (S, nsteps))):
+        raise _capi.NativeLibraryError("fnm_coeff: fvals must be contiguous float64 %s"
+                                       % ("(S, nsteps, 2)" if cplx else "(S, nsteps)"))
+    C = torch.empty((S, nsteps, 2) if cplx else (S, nsteps), dtype=torch.float64, device=Qt.device)
+    tail = torch.empty((S,), dtype=torch.float64, device=Qt.device)
+    rc = call("xk_fnm_coeff", None, ptr(Qt), ptr(theta), ptr(state), ptr(fvals), ptr(C), ptr(tail), ptr(flag), S,
+              nsteps, int(k), int(fn_code), float(param), 1 if cplx else 0, raw=raw)
+    if raw:
+        return rc
+    return C, tail
+
+
+def fnm_step(W, r2, r1, X, C, Tal, Tbe, state, S, N, ld, nblk, nsteps, k, kstate, last=False, raw=False):
+    """step k of pass 2: X += (C[:, k] / Tbe[:, k]) r2, then (unless last) r1 <- the Lanczos vector of step k + 1 from
+    the recorded Tal, Tbe, bit for bit the one xk_slq_step wrote.  m and the flag come from state slot kstate & 1.
+    W = None means last.  The caller swaps r1 and r2."""
+    require_device(X, "vector")
+    return call("xk_fnm_step", X.dtype, ptr(W), ptr(r2), ptr(r1), ptr(X), ptr(C), ptr(Tal), ptr(Tbe), ptr(state), S, N,
+                ld, nblk, int(nsteps), int(k), int(kstate), 1 if last else 0, raw=raw)
+
+
 # --------------------------------------------------------------------------- Chebyshev filter step (xk_cheb.hip)
 def cheb_step(AY, Y, Yprev, coef, out=None, N=None, raw=False):
     """out[b,c,:N] = coef[b,0] * AY[b,c,:N] + coef[b,1] * Y[b,c,:N] + coef[b,2] * Yprev[b,c,:N]  (xk_cheb_step_*): the

@@ -9,14 +9,18 @@ The recurrence is the kernels' (xk_slq.hip): Lanczos on the un-normalised vector
 Shared with the native driver and the public functions: the argument checks (`check_options`), the probes
 (`draw_probes`: drawn on the host from a generator of their own, the same numbers for a host and a device run) and the
 sum over the nodes for a Python callable (`sum_nodes`, any device).
+
+`funm` is the host twin of `native_fnm.funm`: f(A) B by two-pass Lanczos.  Pass 1 is `lanczos`; the coefficients of
+f(A) b in the Lanczos basis come from `torch.linalg.eigh` of the small matrix (`eigvecs`, `coefficients`); `replay` runs
+the recurrence again from the recorded scalars, by the expressions of `lanczos`, and accumulates X.
 """
 import torch
 from xitorch_amd._util import bcast_shape
 
-__all__ = ["forms", "check_options", "draw_probes", "sum_nodes", "calls", "FN_NAMES", "NEEDS_POSITIVE", "MAX_STEPS",
-           "BREAK"]
+__all__ = ["forms", "funm", "check_options", "draw_probes", "sum_nodes", "node_values", "calls", "FN_NAMES",
+           "NEEDS_POSITIVE", "MAX_STEPS", "BREAK"]
 
-calls = {"forms": 0}
+calls = {"forms": 0, "funm": 0}
 MAX_STEPS = 128                        # the projected matrix of xk_slq_quad lives on chip
 BREAK = 64.0                           # SQ_BREAK of xk_slq.hip
 FN_NAMES = ("log", "inv", "sqrt", "invsqrt", "exp", "identity")
@@ -188,3 +192,111 @@ def forms(A, Z, opt):
         q = sum_nodes(theta, weight, mf, zf, named_fn(fn, opt["t"]))
         q = torch.where(bad, torch.full_like(q, float("nan")), q)
     return q.reshape(*bdims, p), bad.reshape(*bdims, p), m.to(torch.int64), napply
+
+
+# ------------------------------------------------------------------------------------------------ f(A) B, two passes
+def node_values(theta, m, fn, cplx, who="funm_multiply"):
+    """a callable `fn` on the nodes, in torch on the arrays' device: (S, nsteps) float64, or complex128 with `cplx`,
+    zero beyond m_s.  As in `sum_nodes`, the unused entries `fn` sees repeat the system's first node (1 for a system
+    without nodes).  A complex result on a real operator is refused."""
+    ns = theta.shape[-1]
+    used = torch.arange(ns, device=theta.device)[None, :] < m[:, None]
+    first = torch.where(m[:, None] > 0, theta[:, :1], torch.ones_like(theta[:, :1]))
+    f = fn(torch.where(used, theta, first))
+    if not isinstance(f, torch.Tensor) or f.shape != theta.shape:
+        raise RuntimeError("%s: a callable fn must map an (S, m) tensor to a tensor of the same shape" % who)
+    if f.is_complex() and not cplx:
+        raise RuntimeError("%s: fn returned complex values on a real operator; cast A to a complex dtype to apply a "
+                           "complex function" % who)
+    f = f.to(torch.complex128 if cplx else torch.float64)
+    return torch.where(used, f, torch.zeros_like(f))
+
+
+def eigvecs(Tal, Tbe, m):
+    """eigenvalues theta (S, nsteps) and eigenvectors Q (S, nsteps, nsteps), Q[s, j, k] = component j of eigenvector k,
+    of every system's m_s x m_s Jacobi matrix by torch.linalg.eigh; entries at and beyond m_s are zero"""
+    S, ns = Tal.shape
+    theta = torch.zeros_like(Tal)
+    Q = torch.zeros((S, ns, ns), dtype=Tal.dtype, device=Tal.device)
+    for mv in torch.unique(m).tolist():
+        mv = int(mv)
+        if mv == 0:
+            continue
+        idx = (m == mv).nonzero().squeeze(-1)
+        T = torch.diag_embed(Tal[idx, :mv])
+        if mv > 1:
+            off = Tbe[idx, 1:mv]
+            T = T + torch.diag_embed(off, offset=1) + torch.diag_embed(off, offset=-1)
+        ev, V = torch.linalg.eigh(T)
+        theta[idx, :mv] = ev
+        Q[idx[:, None, None], torch.arange(mv)[None, :, None], torch.arange(mv)[None, None, :]] = V
+    return theta, Q
+
+
+def coefficients(Q, f, m, zz):
+    """C[s, j] = |b_s| sum_k Q[s, j, k] f[s, k] Q[s, 0, k] and tail[s] = |C[s, m-4:m]| / |C[s, :m]| (0 when m <= 4)"""
+    C = torch.sqrt(zz)[:, None] * torch.einsum("sjk,sk->sj", Q.to(f.dtype), f * Q[:, 0, :])
+    ar = torch.arange(C.shape[-1], device=C.device)[None, :]
+    a2 = C.abs() ** 2
+    last4 = torch.where((ar >= m[:, None] - 4) & (ar < m[:, None]), a2, torch.zeros_like(a2)).sum(-1)
+    tail = torch.where(m > 4, torch.sqrt(last4 / a2.sum(-1)), torch.zeros_like(last4))
+    return C, tail
+
+
+def replay(A, Z, Tal, Tbe, m, zz, C):
+    """pass 2: the recurrence of `lanczos` once more from the recorded Tal, Tbe (*bdims, p, nsteps), accumulating
+    X = sum_k (C[..., k] / beta_k) r2_k.  Every expression that forms a vector is the one of `lanczos`, so the vectors
+    are the same bits.  Returns X and the number of operator applies."""
+    rdt = _real_dtype(Z.dtype)
+    sc = lambda s: s.to(rdt)
+    r2, r1 = Z.clone(), torch.zeros_like(Z)
+    X = torch.zeros_like(Z)
+    mk, nz = m.unsqueeze(-2), (zz != 0).unsqueeze(-2)
+    one = torch.ones_like(zz).unsqueeze(-2)
+    kmax = int(m.max()) if m.numel() else 0
+    napply = 0
+    for k in range(kmax):
+        live = nz & (mk > k)
+        alpha, beta = Tal[..., k].unsqueeze(-2), Tbe[..., k].unsqueeze(-2)
+        sb = torch.where(live, beta, one)
+        X = torch.where(live, X + (C[..., k].unsqueeze(-2) / sb).to(Z.dtype) * r2, X)
+        if k + 1 == kmax:                                                      # the last step needs no product
+            break
+        W = A.mm(r2)
+        napply += 1
+        y = W * sc(1.0 / sb) - sc(alpha / sb) * r2
+        if k > 0:
+            y = y - sc(sb / torch.where(live, Tbe[..., k - 1].unsqueeze(-2), one)) * r1
+        r1, r2 = torch.where(live, r2, r1), torch.where(live, y, r2)
+    return X, napply
+
+
+def funm(A, B, opt):
+    """f(A) b_j for every column of B (*BB, n, p) in host memory.  Returns X (*BAB, n, p), the flags (*BAB, p) of
+    native_fnm.funm (int64; here only bit 0: a node <= 0 under a function that needs positivity, the column is NaN; eigh
+    has no non-convergence flag), the step counts, the tails (*BAB, p) and the
+    number of operator applies."""
+    calls["funm"] += 1
+    if torch.device(A.device).type != "cpu":
+        raise RuntimeError("host_slq serves operators in host memory only (operator is on %s)" % (A.device,))
+    n, p = A.shape[-1], B.shape[-1]
+    bdims = list(bcast_shape(A.shape[:-2], B.shape[:-2]))
+    Bb = B.to(A.dtype).expand(*bdims, n, p)
+    Tal, Tbe, m, zz, napply = lanczos(A, Bb, opt["nsteps"], bdims)
+    ns = Tal.shape[-1]
+    mf, zf = m.reshape(-1), zz.reshape(-1)
+    theta, Q = eigvecs(Tal.reshape(-1, ns), Tbe.reshape(-1, ns), mf)
+    fn, cplx = opt["fn"], A.dtype.is_complex
+    bad = torch.zeros_like(mf, dtype=torch.bool)
+    if callable(fn):
+        f = node_values(theta, mf, fn, cplx)
+    else:
+        if fn in NEEDS_POSITIVE:
+            used = torch.arange(ns)[None, :] < mf[:, None]
+            bad = (used & ~(theta > 0)).any(-1)
+            theta = torch.where(used & (theta > 0), theta, torch.ones_like(theta))
+        f = node_values(theta, mf, named_fn(fn, opt["t"]), cplx)
+    C, tail = coefficients(Q, f, mf, zf)
+    C = torch.where(bad[:, None], torch.full_like(C, float("nan")), C)
+    X, nap2 = replay(A, Bb, Tal, Tbe, m, zz, C.reshape(*bdims, p, ns))
+    return X, bad.to(torch.int64).reshape(*bdims, p), m.to(torch.int64), tail.reshape(*bdims, p), napply + nap2

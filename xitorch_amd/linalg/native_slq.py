@@ -13,7 +13,7 @@ Three vectors per system whatever the step count (the probe panel becomes r1 aft
 stored basis, no reorthogonalisation.  The host reads NOTHING inside the run: after nsteps steps xk_slq_quad turns every
 (Tal, Tbe) into nodes, weights and the sum on the device, and the caller reads the results once.
 
-Not built: f(A) B itself, reorthogonalisation, preconditioned or M-weighted quadrature, batch sharding.
+Not built: reorthogonalisation (f(A) B itself is native_fnm.py), preconditioned or M-weighted quadrature, batch sharding.
 """
 import torch
 from xitorch_amd import kernels as K
