@@ -190,6 +190,9 @@ __global__ __launch_bounds__(1024) void tridiag_eigh_kernel(
     for (int q = j - 1; q >= 0; --q) {
       if (lamv[j] - lamv[q] < T(10) * eps * tnorm) shift += T(10) * eps * tnorm; else break;
     }
+    // (the head of a cluster moves too, away from its followers: on lamv[j] itself every solve would redraw its direction
+    // inside the cluster's invariant subspace and the followers' Gram-Schmidt pass would cancel; see xk_eigh_big.hip)
+    if (shift == lamv[j] && j + 1 < p && lamv[j + 1] - lamv[j] < T(10) * eps * tnorm) shift -= T(10) * eps * tnorm;
     T* dl = lu + ((long)0 * n) * p + j;
     T* dg = lu + ((long)1 * n) * p + j;
     T* du = lu + ((long)2 * n) * p + j;
