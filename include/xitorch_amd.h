@@ -750,6 +750,41 @@ int xk_gkl_bsvd(const double* Bm, const double* beta, const double* smax, const 
                 int keep, int descending, double tol, double* sigma, double* P, double* Q, double* res, int* status,
                 double* Bnext, void* stream);
 
+/* ---- Krylov-Schur Arnoldi for non-Hermitian eigenpairs (extension: linalg.eigs; new symbols only, ABI stays 2) ------
+ * The Arnoldi step orthogonalises with xk_gkl_sweep_* above.  The projected matrix H is (Bt, m + 1, m) row-major
+ * DOUBLES on the device: real for real operators, interleaved (re, im) for complex ones (cplx != 0).
+ * xk_arn_finish: xk_gkl_finish — the same fixed-order sums, norm, reciprocal, running maximum and breakdown flag, bit
+ *   for bit — with one more output: when hcol is given, sum_r (r < nval - 1) is also stored (accumulate == 0) or added
+ *   (accumulate == 1) at hcol[b * sHb + r * sHr] (real) or hcol[b * sHb + (r / 2) * sHr + r % 2] (cplx: r runs over
+ *   re, im pairs), strides in doubles: the column j of H, hcol = &H[0, 0, j], sHr = m (2 m for cplx).  The Arnoldi
+ *   column is the sum of the coefficients of the two projecting passes; dst = &H[0, j + 1, j] receives the norm.
+ *   XK_ERR_ARG: what xk_gkl_finish refuses, cplx / accumulate not 0 or 1, cplx with an even nval, sHr below one
+ *   entry, Bt > 1 with members of the column overlapping.
+ * xk_arn_schur: one workgroup per member, complex double in LDS, m <= xk_arn_max_rows().  With B = H[b, :m, :m] and
+ *   beta = H[b, m, m - 1]: Schur form B = Z T Z^H (Householder reduction to Hessenberg form, single-shift QR with
+ *   Wilkinson and exceptional shifts, at most 30 m iterations), the eigenvalues ranked by which (0 largest modulus, 1
+ *   largest real part, 2 smallest real part, 3 largest imaginary part, 4 smallest imaginary part; 3 and 4 for cplx
+ *   only) and the first keep' brought to the leading positions of T.  keep' = keep + keep_add[b] (keep_add may be
+ *   NULL), moved by one when the cut would separate a complex-conjugate pair of a real B (partners share their rank,
+ *   positive imaginary part first), never above m - 1.  Outputs: theta (Bt, m) complex, in rank order; Y (Bt, m, neig)
+ *   complex, unit Ritz vectors of the first neig (columns); res (Bt, neig) = |beta| |Y[m - 1, i]|; Q (Bt, m, m) in
+ *   H's element type, the restart coefficients in columns < keep' (the rest 0): Z[:, :keep'] for cplx, for a real B a
+ *   REAL orthonormal basis of the same space (column-pivoted Gram-Schmidt, applied twice, of [Re Z | Im Z]); Hnext
+ *   (Bt, m + 1, m), not H: Q^H B Q in the leading block, beta Q[m - 1, :keep'] in row keep', 0 elsewhere; status
+ *   (Bt, xk_arn_status_words()) = {number of i < neig with res <= tol * max(|theta_i|, u |B|_F), QR iterations, flags,
+ *   keep', brk[b] (brk NULL: -1), 0, 0, 0}.  Flags: 1 a non-finite entry (nothing else is written), 2 the QR
+ *   iteration limit was hit (nothing else is written), 4 the real basis does not close under conjugation (a column
+ *   longer than 1e-8 is left after keep' vectors: call again with keep_add[b] one larger), 8 keep' != keep.
+ *   XK_ERR_ARG: m < 2 or beyond the cap, not 1 <= neig <= keep <= m - 1, which out of range, a null output. */
+int xk_arn_max_rows(void);
+int xk_arn_status_words(void);
+int xk_arn_finish(const double* part, int Bt, int nval, int nchunk, double* coef, long sC, double* nrm, double* rnrm,
+                  double* hcol, long sHb, long sHr, int cplx, int accumulate, double* dst, long sdst, double* smax,
+                  double u, int* brk, int code, void* stream);
+int xk_arn_schur(const double* H, int Bt, int m, int neig, int keep, const int* keep_add, int which, int cplx,
+                 double tol, double u, const int* brk, double* theta, double* Y, double* res, double* Q, double* Hnext,
+                 int* status, void* stream);
+
 /* ---- factorised sparse approximate inverse of a Hermitian CSR operator (extension: linalg.fsai; new symbols only, ABI
  * stays 2) -----------------------------------------------------------------------------------------------------------
  * xk_fsai_build: the values of the lower-triangular G with G A G^H ~ I on a given pattern.  Row i of G has the columns

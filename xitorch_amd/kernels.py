@@ -1489,6 +1489,82 @@ def gkl_bsvd(Bm, beta=None, smax=None, brk=None, k=0, keep=0, descending=True, t
     return rc if raw else out
 
 
+# --------------------------------------------------------------------------- Krylov-Schur Arnoldi kernels (xk_arn.hip)
+ARN_WHICH = {"LM": 0, "LR": 1, "SR": 2, "LI": 3, "SI": 4}
+ARN_FLAG_NONFINITE, ARN_FLAG_QR_LIMIT, ARN_FLAG_NOT_CLOSED, ARN_FLAG_KEEP_MOVED = 1, 2, 4, 8
+
+
+def arn_max_rows():
+    """largest order of the projected matrix xk_arn_schur serves (= the largest ncv of eigs)"""
+    return int(fn("xk_arn_max_rows")())
+
+
+def arn_status_words():
+    return int(fn("xk_arn_status_words")())
+
+
+def arn_finish(part, Bt, nval, nchunk, coef, nrm, rnrm, hcol=None, accumulate=False, dst=None, smax=None, u=0.0,
+               brk=None, code=0, raw=False):
+    """gkl_finish with the dots also stored in (accumulate: added to) a column of the projected matrix (xk_arn_finish).
+    hcol: the (Bt, rows) float64 or (Bt, rows) complex128 VIEW H[:, :rows, j] of the (Bt, m + 1, m) Hessenberg matrix
+    (None: not stored); dst: the (Bt,) float64 view that receives the norm (H[:, j + 1, j], or its real part)."""
+    require_device(part, "partials")
+    sdst = sHb = sHr = cplx = 0
+    if dst is not None:
+        if dst.dtype != torch.float64 or dst.dim() != 1 or dst.shape[0] != Bt:
+            raise _capi.NativeLibraryError("arn_finish: dst must be a (Bt,) float64 view")
+        sdst = dst.stride(0) if Bt > 1 else 0
+    if hcol is not None:
+        cplx = 1 if hcol.is_complex() else 0
+        if hcol.dtype not in (torch.float64, torch.complex128) or hcol.dim() != 2 or hcol.shape[0] != Bt or \
+                hcol.shape[1] * (2 if cplx else 1) != nval - 1:
+            raise _capi.NativeLibraryError("arn_finish: hcol must be a (Bt, rows) float64 / complex128 view of nval - 1 "
+                                           "doubles per member")
+        mul = 2 if cplx else 1
+        sHb, sHr = (hcol.stride(0) * mul if Bt > 1 else 0), hcol.stride(1) * mul
+    return call("xk_arn_finish", None, ptr(part), Bt, int(nval), int(nchunk), ptr(coef),
+                0 if (coef is None or Bt == 1) else coef.stride(0), ptr(nrm), ptr(rnrm), ptr(hcol), sHb, sHr, cplx,
+                1 if accumulate else 0, ptr(dst), sdst, ptr(smax), float(u), ptr(brk), int(code), raw=raw)
+
+
+def arn_schur(H, neig, keep, which="LM", tol=0.0, u=0.0, keep_add=None, brk=None, Hnext=None, out=None, raw=False):
+    """Schur form, ranking, reordering, Ritz data and restart coefficients of the (Bt, m + 1, m) float64 / complex128
+    projected matrices of an Arnoldi cycle, in LDS (xk_arn_schur), m <= arn_max_rows().  Returns (theta (Bt, m)
+    complex128 in rank order, Y (Bt, m, neig) complex128 unit Ritz vectors as columns, res (Bt, neig) = |beta Y[m-1, :]|,
+    Q (Bt, m, m) in H's dtype with the restart coefficients in its first keep' columns, status (Bt, 8) int32 =
+    converged among the first neig / QR iterations / flags / keep' / breakdown code).  Hnext: receives the projected
+    matrix of the restarted basis.  keep_add: (Bt,) int32 added to keep per member.  out: the five outputs to reuse."""
+    require_device(H, "projected matrix")
+    if H.dtype not in (torch.float64, torch.complex128) or H.dim() != 3 or H.shape[1] != H.shape[2] + 1 or \
+            not H.is_contiguous():
+        raise _capi.NativeLibraryError("arn_schur: H must be a contiguous (Bt, m + 1, m) float64 / complex128 tensor")
+    if which not in ARN_WHICH:
+        raise _capi.NativeLibraryError("arn_schur: which must be one of %s" % sorted(ARN_WHICH))
+    Bt, m = H.shape[0], H.shape[2]
+    if Hnext is None:
+        Hnext = torch.empty_like(H)
+    if Hnext.shape != H.shape or Hnext.dtype != H.dtype or not Hnext.is_contiguous():
+        raise _capi.NativeLibraryError("arn_schur: Hnext must be a contiguous tensor of H's shape and dtype")
+    if out is None:
+        mk = lambda dt, *s: torch.zeros(s, dtype=dt, device=H.device)
+        out = (mk(torch.complex128, Bt, m), mk(torch.complex128, Bt, m, int(neig)), mk(torch.float64, Bt, int(neig)),
+               mk(H.dtype, Bt, m, m), mk(torch.int32, Bt, 8))
+    theta, Y, res, Q, status = out
+    want = ((theta, torch.complex128, (Bt, m)), (Y, torch.complex128, (Bt, m, int(neig))),
+            (res, torch.float64, (Bt, int(neig))), (Q, H.dtype, (Bt, m, m)), (status, torch.int32, (Bt, 8)))
+    for t, dt, shape in want:
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != H.device:
+            raise _capi.NativeLibraryError("arn_schur: an output is not a contiguous %s tensor of shape %s on H's device"
+                                           % (dt, shape))
+    for t, n in ((keep_add, "keep_add"), (brk, "brk")):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < Bt or not t.is_contiguous() or t.device != H.device):
+            raise _capi.NativeLibraryError("arn_schur: %s must be a contiguous (Bt,) int32 tensor on H's device" % n)
+    rc = call("xk_arn_schur", None, ptr(H), Bt, m, int(neig), int(keep), ptr(keep_add), ARN_WHICH[which],
+              1 if H.is_complex() else 0, float(tol), float(u), ptr(brk), ptr(theta), ptr(Y), ptr(res), ptr(Q),
+              ptr(Hnext), ptr(status), raw=raw)
+    return rc if raw else out
+
+
 # --------------------------------------------------------------------------- FSAI preconditioner build
 def fsai_max_row():
     return int(fn("xk_fsai_max_row")())

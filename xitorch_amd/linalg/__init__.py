@@ -4,6 +4,7 @@ from xitorch_amd.linalg.precond import fsai, FSAIOperator
 from xitorch_amd.linalg.lstsq import lstsq
 from xitorch_amd.linalg.slq import quadform, trace_fn, logdet
 from xitorch_amd.linalg.fnm import funm_multiply, expm_multiply
+from xitorch_amd.linalg.eigs import eigs
 
 __all__ = ["solve", "symeig", "lsymeig", "usymeig", "svd", "fsai", "FSAIOperator", "lstsq", "quadform", "trace_fn",
-           "logdet", "funm_multiply", "expm_multiply"]
+           "logdet", "funm_multiply", "expm_multiply", "eigs"]

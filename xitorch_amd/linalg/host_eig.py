@@ -1111,3 +1111,323 @@ def lobpcg(A, neig, mode, M=None, max_niter=200, min_eps=1e-6, nguard=None, prec
     if mode != "lowest":
         evals, evecs = evals.flip(-1), evecs.flip(-1)
     return evals, evecs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Krylov-Schur Arnoldi for non-Hermitian eigenpairs (extension; Stewart, SIAM J. Matrix Anal. Appl. 23 (2001) 601):
+# eigs(method="arnoldi")
+# ---------------------------------------------------------------------------------------------------------------------
+__all__ += ["arnoldi", "arn_default_ncv"]
+calls.setdefault("arnoldi", 0)
+ARN_MAX_NCV = 48             # order of the projected matrix the native small Schur kernel serves (xk_arn_schur)
+ARN_WHICH = ("LM", "LR", "SR", "LI", "SI")
+ARN_PAIR_RTOL = 1e-6         # two eigenvalues of a real matrix are conjugate partners within this relative distance
+ARN_CLOSED_TOL = 1e-8        # a column of [Re Z | Im Z] longer than this outside the real basis: the pairing misjudged
+
+
+def arn_default_ncv(neig, n):
+    """basis size: min(max(2 neig + 8, 20), n)"""
+    return min(max(2 * neig + 8, 20), n)
+
+
+def _arn_check(A, neig, which, M, process_group):
+    """the refusals every route of eigs shares (the dense one included); returns (n, neig)"""
+    if M is not None:
+        raise NotImplementedError("eigs: the generalised problem (M=) is not supported")
+    if process_group is not None:
+        raise NotImplementedError("eigs: batch sharding over a process group is not supported")
+    if A.shape[-1] != A.shape[-2]:
+        raise RuntimeError("eigs: the operator must be square, got %s" % (tuple(A.shape),))
+    if which == "SM":
+        raise ValueError("eigs: which='SM' needs shift-and-invert, which is not built; for the eigenvalues nearest 0 "
+                         "run eigs on an operator that applies the inverse and take 1 / lambda")
+    if which not in ARN_WHICH:
+        raise ValueError("eigs: which must be one of %s, got %r" % (", ".join(ARN_WHICH), which))
+    if which in ("LI", "SI") and not A.dtype.is_complex:
+        raise ValueError("eigs: which=%r is for complex operators; the spectrum of a real operator is symmetric about "
+                         "the real axis" % which)
+    n = A.shape[-1]
+    if neig is None or neig < 1 or neig > n:
+        raise ValueError("eigs: neig = %r eigenpairs asked of an operator of order %d" % (neig, n))
+    return n, int(neig)
+
+
+def _arn_setup(A, neig, which, ncv, M, process_group):
+    """argument checks and sizes shared by the host twin and the device driver: (n, neig, ncv, keep, dense) with dense
+    = the problem is handed to the dense eigensolver (n <= max(2 neig, 16))."""
+    n, neig = _arn_check(A, neig, which, M, process_group)
+    dense = n <= max(2 * neig, 16)
+    if ncv is None:
+        ncv = arn_default_ncv(neig, n)
+        if not dense and ncv > ARN_MAX_NCV:
+            raise ValueError("eigs: neig = %d needs a basis of %d > %d vectors, beyond the native small Schur kernel; "
+                             "pass a smaller ncv (>= neig + 2)" % (neig, ncv, ARN_MAX_NCV))
+    ncv = int(ncv)
+    if not dense:
+        if ncv > ARN_MAX_NCV:
+            raise ValueError("eigs: ncv = %d is beyond the native small Schur kernel (ncv <= %d)" % (ncv, ARN_MAX_NCV))
+        if neig > ncv - 2:
+            raise ValueError("eigs: neig = %d needs ncv >= neig + 2 (got ncv = %d)" % (neig, ncv))
+        if ncv > n:
+            raise ValueError("eigs: ncv = %d exceeds the order %d of the operator" % (ncv, n))
+    keep = neig + (ncv - neig) // 2
+    return n, neig, ncv, keep, dense
+
+
+def _arn_key(lam, which):
+    if which == "LM":
+        return lam.abs()
+    if which in ("LR", "SR"):
+        return lam.real if which == "LR" else -lam.real
+    return lam.imag if which == "LI" else -lam.imag
+
+
+def _arn_order(lam, which, real_op):
+    """The ranking of xk_arn_schur on one member's eigenvalues lam (m,) complex128 (host): (order, partner) with order
+    the indices best first by `which`.  For a real operator an eigenvalue and the nearest one of opposite imaginary
+    part, if it is its conjugate to ARN_PAIR_RTOL, are partners: they share the larger key and stay adjacent, positive
+    imaginary part first."""
+    m = lam.shape[0]
+    key = _arn_key(lam, which).tolist()
+    re, im = lam.real.tolist(), lam.imag.tolist()
+    partner = [-1] * m
+    if real_op:
+        for i in range(m):
+            if partner[i] >= 0 or im[i] == 0.0:
+                continue
+            best, bd = -1, 0.0
+            for j in range(m):
+                if j == i or partner[j] >= 0 or not im[j] * im[i] < 0.0:
+                    continue
+                d = math.hypot(re[j] - re[i], im[j] + im[i])
+                if best < 0 or d < bd:
+                    best, bd = j, d
+            if best >= 0 and bd <= ARN_PAIR_RTOL * max(math.hypot(re[i], im[i]), math.hypot(re[best], im[best])):
+                partner[i], partner[best] = best, i
+    skey = [max(key[i], key[partner[i]]) if partner[i] >= 0 else key[i] for i in range(m)]
+    lead = [min(i, partner[i]) if partner[i] >= 0 else i for i in range(m)]
+    order = sorted(range(m), key=lambda i: (-skey[i], lead[i], -im[i], i))
+    return order, partner
+
+
+def _arn_cut(order, partner, keep, m):
+    """keep' of xk_arn_schur: keep, moved by one when the cut separates partners, never above m - 1"""
+    kp = min(keep, m - 1)
+    if partner[order[kp - 1]] == order[kp]:
+        kp += 1
+    if kp > m - 1:
+        kp = m - 1
+        if partner[order[kp - 1]] == order[kp]:
+            kp -= 1
+    return kp
+
+
+def _arn_complex_dtype(dtype):
+    return torch.complex128 if dtype in (torch.float64, torch.complex128) else torch.complex64
+
+
+def _arn_select(evals, evecs, neig, which, real_op, out_dtype):
+    """the first neig eigenpairs of every member in the order of `which`; evals (B, m), evecs (B, n, m) complex"""
+    ev, vec = evals.to("cpu", torch.complex128), evecs
+    idx = torch.tensor([_arn_order(ev[b], which, real_op)[0][:neig] for b in range(ev.shape[0])], dtype=torch.int64)
+    idx = idx.to(evals.device)
+    lam = torch.gather(evals, 1, idx)
+    X = torch.gather(vec, 2, idx.unsqueeze(1).expand(-1, vec.shape[1], -1))
+    X = X / torch.linalg.vector_norm(X, dim=1, keepdim=True)
+    return lam.to(out_dtype), X.to(out_dtype)
+
+
+def _arn_dense(A, neig, which):
+    """the dense route (method="exacteig" and the hand-over of small problems): the library eigensolver on the full
+    matrix, in host memory (the general eigenproblem has no device route here), and the same selection"""
+    full = A.fullmatrix()
+    bdims, n = list(full.shape[:-2]), full.shape[-1]
+    cdt = _arn_complex_dtype(A.dtype)
+    ev, vec = torch.linalg.eig(full.reshape(-1, n, n).to("cpu"))
+    lam, X = _arn_select(ev, vec, neig, which, not A.dtype.is_complex, cdt)
+    return lam.reshape(*bdims, neig).to(full.device), X.reshape(*bdims, n, neig).to(full.device)
+
+
+def _arn_start_vector(A, V0, v_init, bdims, B, n, dtype, dev, rng_device):
+    """(B, n) start vector; V0 (*batch, n, k0) holds guesses of eigenvectors: their sum starts the iteration (the real
+    part of the sum for a real operator)"""
+    if V0 is not None:
+        if V0.shape[-2] != n:
+            raise RuntimeError("V0 must have shape (*batch, %d, k0), got %s" % (n, tuple(V0.shape)))
+        v = V0.sum(dim=-1, keepdim=True)
+        if v.is_complex() and not dtype.is_complex:
+            v = v.real
+        v = v.to(device=dev, dtype=dtype)
+        return v.expand(*bdims, n, 1).reshape(B, n)
+    return _initial_block(v_init, None, bdims, B, n, 1, dtype, dev, rng_device).reshape(B, n)
+
+
+def _arn_true_residuals(apply_cols, X, lam, real_op):
+    """|A x_i - theta_i x_i| per pair in the output precision; X (B, n, k) complex, apply_cols maps (B, n, p) of the
+    OPERATOR's dtype to A times it"""
+    if real_op:
+        k = X.shape[-1]
+        AX = apply_cols(torch.cat([X.real, X.imag], dim=-1).contiguous())
+        AX = torch.complex(AX[..., :k], AX[..., k:])
+    else:
+        AX = apply_cols(X)
+    return torch.linalg.vector_norm(AX - X * lam.unsqueeze(-2), dim=-2)
+
+
+def _arn_finish_report(resid, lam, hfro, u_round, min_eps, niter, done):
+    """the one ConvergenceWarning of a call: pairs whose true residual misses the bound by more than a factor 2"""
+    import warnings
+    from xitorch_amd._util import ConvergenceWarning
+    bound = min_eps * torch.maximum(lam.abs().to(torch.float64), (u_round * hfro).unsqueeze(-1))
+    nmiss = int((~(resid.to(torch.float64) <= 2.0 * bound)).sum())
+    if nmiss or not done:
+        worst = float((resid.to(torch.float64) / torch.clamp(bound, min=1e-300)).max())
+        warnings.warn(ConvergenceWarning("eigs: %d of %d eigenpairs miss |A x - theta x| <= min_eps max(|theta|, u |H|_F) "
+                                         "by more than a factor 2 after %d restart cycles (worst ratio %.3e, min_eps = "
+                                         "%.3e); the last Ritz block is returned"
+                                         % (nmiss, resid.numel(), niter, worst, min_eps)))
+    return nmiss
+
+
+def arnoldi(A, neig, which="LM", max_niter=100, min_eps=1e-6, ncv=None, V0=None, v_init="randn", rng_device="cpu",
+            verbose=False, trace=None, M=None, process_group=None, **unused):
+    """Krylov-Schur Arnoldi in torch ops for an operator in HOST memory: the statement of `native_arnoldi.arnoldi`
+    (same options, same refusals, same decisions).  One Arnoldi vector per member and step, orthogonalised against the
+    whole basis by two classical Gram-Schmidt passes, the column of H the sum of their coefficients.  A cycle fills
+    the basis to ncv vectors; the small problem goes through the library's eig: the wanted eigenvectors' span is that
+    of the reordered Schur vectors the device kernel keeps, and an orthonormal basis of it (QR; for a real operator a
+    real basis of [Re | Im] by SVD) restarts the iteration with H = Q^H B Q and the spike beta Q[m-1, :].  Returns
+    (evals (*B, neig), evecs (*B, n, neig)), complex."""
+    calls["arnoldi"] += 1
+    dev = torch.device(A.device)
+    if dev.type != "cpu":
+        raise NativeLibraryError("host_eig serves operators in host memory only (operator is on %s): device operators "
+                                 "run on the HIP kernels" % dev)
+    n, neig, ncv, keep, dense = _arn_setup(A, neig, which, ncv, M, process_group)
+    if dense:
+        if trace is not None:
+            trace.update(niter=0, napply=0, ncv=ncv, handed_to="dense_eig")
+        return _arn_dense(A, neig, which)
+    dtype = A.dtype
+    real_op = not dtype.is_complex
+    cdt = _arn_complex_dtype(dtype)
+    hdt = torch.float64 if real_op else torch.complex128
+    bdims = list(A.shape[:-2])
+    B = 1
+    for d in bdims:
+        B *= d
+    rdt = torch.float64 if dtype in (torch.float64, torch.complex128) else torch.float32
+    u_round = torch.finfo(rdt).eps
+    napply = 0
+    m = ncv
+
+    def apply_cols(X):
+        # (B, n, p) -> A X
+        nonlocal napply
+        napply += 1
+        Y = A.mm(X.reshape(*bdims, n, X.shape[-1]))
+        return Y.expand(*bdims, n, X.shape[-1]).reshape(B, n, X.shape[-1])
+
+    V = torch.zeros((B, n, m + 1), dtype=dtype)
+    H = torch.zeros((B, m + 1, m), dtype=hdt)
+    smax = torch.zeros((B,), dtype=torch.float64)
+    gen = torch.Generator().manual_seed(12421 + 11)
+    breakdowns = []
+
+    def project(w, Q):
+        c = torch.matmul(_H(Q), w.unsqueeze(-1))
+        return w - torch.matmul(Q, c).squeeze(-1), c.squeeze(-1)
+
+    def step(j, kps):
+        # members whose restart kept more than j vectors (kps[b] > j) hold column j already: the step leaves them alone
+        nonlocal smax
+        live = torch.tensor([kp <= j for kp in kps])
+        Q = V[:, :, :j + 1]
+        w = apply_cols(V[:, :, j:j + 1]).squeeze(-1)
+        w, c1 = project(w, Q)
+        w, c2 = project(w, Q)
+        nrm = torch.linalg.vector_norm(w, dim=-1).to(torch.float64)
+        bad = (~(nrm > u_round * smax) | ~torch.isfinite(nrm)) & live
+        if bool(bad.any()):
+            breakdowns.append((j, bad.nonzero().flatten().tolist()))
+            r = _gkl_random(gen, B, n, dtype)
+            r, _ = project(r, Q)
+            r, _ = project(r, Q)
+            r = r / torch.linalg.vector_norm(r, dim=-1, keepdim=True)
+            w = torch.where(bad.unsqueeze(-1), r, w / torch.where(bad, torch.ones_like(nrm), nrm).to(rdt).unsqueeze(-1))
+            nrm = torch.where(bad, torch.zeros_like(nrm), nrm)
+        else:
+            w = w / nrm.to(rdt).unsqueeze(-1)
+        smax = torch.where(live, torch.maximum(smax, nrm), smax)
+        col = H[:, :, j].clone()
+        col[:, :j + 1] = (c1 + c2).to(hdt)
+        col[:, j + 1] = nrm.to(hdt)
+        H[:, :, j] = torch.where(live.unsqueeze(-1), col, H[:, :, j])
+        V[:, :, j + 1] = torch.where(live.unsqueeze(-1), w, V[:, :, j + 1])
+
+    v0 = _arn_start_vector(A, V0, v_init, bdims, B, n, dtype, dev, rng_device)
+    nv0 = torch.linalg.vector_norm(v0, dim=-1, keepdim=True)
+    if bool((nv0 == 0).any()):
+        raise RuntimeError("eigs: the start vector is zero")
+    V[:, :, 0] = v0 / nv0
+    niter, history, kept, done = 0, [], [], False
+    kps = [0] * B                                   # vectors every member kept at its last restart
+    for cycle in range(max_niter):
+        niter = cycle + 1
+        for j in range(min(kps), m):
+            step(j, kps)
+        Bm, beta = H[:, :m, :m], H[:, m, m - 1]
+        theta, Yv = torch.linalg.eig(Bm)
+        hfro = torch.linalg.matrix_norm(Bm).to(torch.float64)
+        orders = [_arn_order(theta[b].to(torch.complex128), which, real_op) for b in range(B)]
+        sel = torch.tensor([o[:neig] for o, _ in orders], dtype=torch.int64)
+        th = torch.gather(theta, 1, sel)
+        Ys = torch.gather(Yv, 2, sel.unsqueeze(1).expand(-1, m, -1))
+        res = beta.abs().unsqueeze(-1) * Ys[:, m - 1, :].abs()
+        bound = min_eps * torch.maximum(th.abs(), (u_round * hfro).unsqueeze(-1))
+        nconv = (res <= bound).sum(dim=-1)
+        history.append(nconv.tolist())
+        if verbose:
+            print("Cycle %3d (basis of %d): converged pairs per member %s" % (niter, m, nconv.tolist()))
+        if bool((nconv >= neig).all()):
+            done = True
+            break
+        if cycle + 1 == max_niter:
+            break
+        # restart: member b keeps its own keep' vectors (a conjugate pair of a real operator is never cut) and
+        # continues from step keep'; `step` leaves the members that are ahead alone
+        Vn = torch.zeros_like(V)
+        Hn = torch.zeros_like(H)
+        kps = []
+        for b in range(B):
+            order, partner = orders[b]
+            kp = _arn_cut(order, partner, keep, m) if real_op else min(keep, m - 1)
+            X = Yv[b][:, order[:kp]]
+            if real_op:
+                while True:
+                    Uu, S_, _ = torch.linalg.svd(torch.cat([X.real, X.imag], dim=-1), full_matrices=False)
+                    if kp >= m - 1 or not (S_.shape[0] > kp and float(S_[kp]) > ARN_CLOSED_TOL):
+                        break
+                    kp += 1                                        # the pairing misjudged: one more vector
+                    X = Yv[b][:, order[:kp]]
+                Qb = Uu[:, :kp].to(hdt)
+            else:
+                Qb, _ = torch.linalg.qr(X)
+            kps.append(kp)
+            Vn[b, :, :kp] = torch.matmul(V[b, :, :m], Qb.to(dtype))
+            Vn[b, :, kp] = V[b, :, m]
+            Hn[b, :kp, :kp] = _H(Qb) @ Bm[b] @ Qb
+            Hn[b, kp, :kp] = beta[b] * Qb[m - 1, :]
+        V, H = Vn, Hn
+        kept.append(list(kps))
+    # Ritz vectors, normalised, and the true residuals from one more apply
+    X = torch.matmul(V[:, :, :m].to(cdt), Ys.to(cdt))
+    X = X / torch.linalg.vector_norm(X, dim=-2, keepdim=True)
+    lam = th.to(cdt)
+    resid = _arn_true_residuals(apply_cols, X, lam, real_op)
+    _arn_finish_report(resid, lam, hfro, u_round, min_eps, niter, done)
+    if trace is not None:
+        trace.update(niter=niter, restarts=niter - 1, napply=napply, ncv=ncv, keep=keep, converged_history=history,
+                     breakdowns=breakdowns, host_reads=None, torch_applies=napply, converged=done,
+                     resid=resid.reshape(*bdims, neig), panel_kernel="host", kept_history=kept)
+    return lam.reshape(*bdims, neig), X.reshape(*bdims, n, neig)
