@@ -812,6 +812,41 @@ int xk_fsai_build_c128(const int* a_ptr, const int* a_idx, const double* a_val, 
 int xk_fsai_build_c64(const int* a_ptr, const int* a_idx, const float* a_val, long sV, int a_nnz, const int* g_ptr,
                       const int* g_idx, float* g_val, long sG, int g_nnz, int* nfail, int N, int B, void* stream);
 
+/* ---- unsymmetric factorised sparse approximate inverse of a CSR operator (extension: linalg.fsai_lu; new symbols only,
+ * ABI stays 2) --------------------------------------------------------------------------------------------------------
+ * xk_fsai_lu_build: the values of the two triangular factors with G_L A G_U ~ I on ONE lower-triangular pattern.  Row i
+ *   has the columns S_i = g_idx[g_ptr[i] .. g_ptr[i+1]): ascending, unique, all <= i, i itself LAST,
+ *   1 <= |S_i| <= xk_fsai_lu_max_row().  With A_SS = A[S_i, S_i] (both triangles as stored), A_SS u = e_m and
+ *   A_SS^T g = e_m from one LU with partial pivoting (pivot: the largest |re| + |im|, ties to the lowest row):
+ *   gl_val holds row i of G_L = g / g_m (unit diagonal), w_val row i of W = G_U^H = conj(u), so that
+ *   (G_L A)[i, j] = 0 and (A G_U)[j, i] = 0 for j in S_i other than i and diag(G_L A G_U) = 1.  The preconditioner is
+ *   P x = G_U (G_L x) = W^H (G_L x), its adjoint P^H x = G_L^H (W x): xk_csr_mm twice.
+ *   Of A (CSR a_ptr (N+1), a_idx, values a_val[b * sV + k], sV = 0 broadcasts one set over the batch) every stored
+ *   entry is read; duplicates add up in storage order, columns need not be sorted, nothing is made real.  a_nnz /
+ *   g_nnz: the stored entries per member of A / of each factor (no index beyond them is read or written).  Factor
+ *   values gl_val[b * sG + k], w_val[b * sG + k].  One wavefront per (row, member), no floating-point atomics:
+ *   bit-reproducible.
+ *   A row with a pivot that is exactly zero or not finite, a u or g that is not finite, or g_m = 0 becomes
+ *   G_L[i, .] = e_i, G_U[., i] = e_i / a_ii (e_i when a_ii, duplicates summed, is zero or not finite) and is counted in
+ *   nfail[b] (B ints, zeroed by the call).  A row of the pattern outside the limits above is left unwritten and
+ *   counted as well: the caller checks the pattern.
+ *   XK_ERR_ARG (decided on the host, before any launch): a null pointer, N <= 0, B <= 0, a negative stride or count,
+ *   g_nnz < N, members of a factor (or of A with sV != 0) that overlap, gl_val or w_val overlapping a_val or each other.
+ *   Complex (_c128 / _c64): interleaved (re, im); strides and counts in whole complex elements. */
+int xk_fsai_lu_max_row(void);
+int xk_fsai_lu_build_f64(const int* a_ptr, const int* a_idx, const double* a_val, long sV, int a_nnz, const int* g_ptr,
+                         const int* g_idx, double* gl_val, double* w_val, long sG, int g_nnz, int* nfail, int N, int B,
+                         void* stream);
+int xk_fsai_lu_build_f32(const int* a_ptr, const int* a_idx, const float* a_val, long sV, int a_nnz, const int* g_ptr,
+                         const int* g_idx, float* gl_val, float* w_val, long sG, int g_nnz, int* nfail, int N, int B,
+                         void* stream);
+int xk_fsai_lu_build_c128(const int* a_ptr, const int* a_idx, const double* a_val, long sV, int a_nnz, const int* g_ptr,
+                          const int* g_idx, double* gl_val, double* w_val, long sG, int g_nnz, int* nfail, int N, int B,
+                          void* stream);
+int xk_fsai_lu_build_c64(const int* a_ptr, const int* a_idx, const float* a_val, long sV, int a_nnz, const int* g_ptr,
+                         const int* g_idx, float* gl_val, float* w_val, long sG, int g_nnz, int* nfail, int N, int B,
+                         void* stream);
+
 /* ---- block Davidson for COMPLEX Hermitian operators (complex64 = _c64, complex128 = _c128; ABI 2) --------------
  * The reference's davidson (xitorch/_impls/linalg/symeig.py:100-227) uses unconjugated transposes and is real-only;
  * these are the complex counterparts of K3t / xk_ritz_residual / the panel CholeskyQR, with conjugate transposes.

@@ -24,54 +24,13 @@
 // makes the row the Jacobi row: G[i,i] = 1 / sqrt(|a_ii|), or 1 when a_ii is 0 or not finite, zeros elsewhere, and
 // one integer atomicAdd on nfail[member].  All sums have a fixed order, all stores are plain vector stores: the
 // result is bit-identical from run to run.
-#include "xk_common.h"
+#include "xk_fsai_el.h"
 
 namespace xk {
 
 constexpr int FSAI_MAX = 32;                                   // longest row of G
 constexpr int FSAI_TRI = FSAI_MAX * (FSAI_MAX + 1) / 2;        // packed lower triangle, elements
 constexpr int FSAI_WAVES = 4;                                  // waves (rows) per workgroup
-
-template <typename T> struct alignas(2 * sizeof(T)) fz { T re, im; };
-
-// the element algebra of the kernel, real and interleaved complex
-template <typename E> struct FsaiEl;
-template <typename T> struct FsaiReal {
-  typedef T real;
-  static __device__ __forceinline__ T zero() { return T(0); }
-  static __device__ __forceinline__ T from_re(T a) { return a; }
-  static __device__ __forceinline__ T re(T a) { return a; }
-  static __device__ __forceinline__ T add(T a, T b) { return a + b; }
-  static __device__ __forceinline__ T msub(T acc, T a, T b) { return acc - a * b; }      // acc - a conj(b)
-  static __device__ __forceinline__ T div_re(T a, T d) { return a / d; }
-  static __device__ __forceinline__ T conj(T a) { return a; }
-  static __device__ __forceinline__ bool finite(T a) { return isfinite(a); }
-  static __device__ __forceinline__ T bcast(T a, int src) { return __shfl(a, src, 64); }
-};
-template <> struct FsaiEl<double> : FsaiReal<double> {};
-template <> struct FsaiEl<float> : FsaiReal<float> {};
-template <typename T> struct FsaiEl<fz<T>> {
-  typedef T real;
-  typedef fz<T> E;
-  static __device__ __forceinline__ E zero() { return {T(0), T(0)}; }
-  static __device__ __forceinline__ E from_re(T a) { return {a, T(0)}; }
-  static __device__ __forceinline__ T re(E a) { return a.re; }
-  static __device__ __forceinline__ E add(E a, E b) { return {a.re + b.re, a.im + b.im}; }
-  static __device__ __forceinline__ E msub(E acc, E a, E b) {                              // acc - a conj(b)
-    return {acc.re - (a.re * b.re + a.im * b.im), acc.im - (a.im * b.re - a.re * b.im)};
-  }
-  static __device__ __forceinline__ E div_re(E a, T d) { return {a.re / d, a.im / d}; }
-  static __device__ __forceinline__ E conj(E a) { return {a.re, -a.im}; }
-  static __device__ __forceinline__ bool finite(E a) { return isfinite(a.re) && isfinite(a.im); }
-  static __device__ __forceinline__ E bcast(E a, int src) { return {__shfl(a.re, src, 64), __shfl(a.im, src, 64)}; }
-};
-
-// LDS written by one lane is read by another lane of the same wave: order the accesses (no workgroup barrier)
-__device__ __forceinline__ void fsai_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ int fsai_tri(int r) { return r * (r + 1) / 2; }
 

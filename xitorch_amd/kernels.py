@@ -1570,9 +1570,11 @@ def fsai_max_row():
     return int(fn("xk_fsai_max_row")())
 
 
-def fsai_check_pattern(g_ptr, g_idx, N):
-    """The contract of xk_fsai_build on the pattern of G, checked once in torch ops: every row has between 1 and
-    xk_fsai_max_row() columns, ascending and unique, none beyond the row index, the row index itself last."""
+def fsai_check_pattern(g_ptr, g_idx, N, cap=None):
+    """The contract of xk_fsai_build (and, with cap = xk_fsai_lu_max_row(), of xk_fsai_lu_build) on the pattern of G,
+    checked once in torch ops: every row has between 1 and `cap` (default xk_fsai_max_row()) columns, ascending and
+    unique, none beyond the row index, the row index itself last."""
+    cap = fsai_max_row() if cap is None else cap
     if g_ptr.dtype != torch.int32 or g_idx.dtype != torch.int32 or g_ptr.dim() != 1 or g_idx.dim() != 1 or \
             g_ptr.numel() != N + 1 or not g_ptr.is_contiguous() or not g_idx.is_contiguous():
         raise _capi.NativeLibraryError("fsai: the pattern of G must be contiguous int32 arrays, g_ptr of N + 1 entries")
@@ -1580,9 +1582,9 @@ def fsai_check_pattern(g_ptr, g_idx, N):
     lens = p[1:] - p[:-1]
     if int(p[0]) != 0 or int(p[-1]) != g_idx.numel() or int(lens.min()) < 1:
         raise _capi.NativeLibraryError("fsai: g_ptr must run from 0 to the entry count and leave no row empty")
-    if int(lens.max()) > fsai_max_row():
+    if int(lens.max()) > cap:
         raise _capi.NativeLibraryError("fsai: a row of G has %d columns, the kernel's cap is %d"
-                                       % (int(lens.max()), fsai_max_row()))
+                                       % (int(lens.max()), cap))
     rows = torch.arange(N, dtype=torch.int64, device=g_ptr.device)
     idx = g_idx.to(torch.int64)
     if not bool((idx[p[1:] - 1] == rows).all()):
@@ -1621,3 +1623,40 @@ def fsai_build(a_ptr, a_idx, a_val, g_ptr, g_idx, N, out=None, nfail=None, check
     rc = call("xk_fsai_build", a_val.dtype, ptr(a_ptr), ptr(a_idx), ptr(a_val), a_val.stride(0) if B > 1 else 0, a_nnz,
               ptr(g_ptr), ptr(g_idx), ptr(out), out.stride(0) if B > 1 else 0, g_nnz, ptr(nfail), int(N), B, raw=raw)
     return rc if raw else (out, nfail)
+
+
+# --------------------------------------------------------------------------- unsymmetric FSAI build
+def fsai_lu_max_row():
+    return int(fn("xk_fsai_lu_max_row")())
+
+
+def fsai_lu_build(a_ptr, a_idx, a_val, g_ptr, g_idx, N, out=None, nfail=None, check_pattern=True, raw=False):
+    """The values of G_L and W = G_U^H on the one pattern (g_ptr, g_idx) for the CSR operator (a_ptr, a_idx, a_val)
+    (xk_fsai_lu_build_*): a_val (B, nnz) rows of unit stride (B = 1 for values shared by a batch: the factors are shared
+    then as well); out = (gl, w), two contiguous (B, g_nnz) tensors; returns (gl, w, nfail (B,) int32 = fallback rows).
+    fp64 / fp32 / complex128 / complex64; complex values must be resolved."""
+    require_device(a_val, "values")
+    if a_val.is_complex():
+        _require_resolved("fsai_lu_build", a_val, *(out or ()))
+    for t in (a_ptr, a_idx, g_ptr, g_idx):
+        if t.dtype != torch.int32 or t.device != a_val.device or not t.is_contiguous():
+            raise _capi.NativeLibraryError("fsai_lu_build: index arrays must be contiguous int32 on the values' device")
+    a_nnz, g_nnz = a_idx.numel(), g_idx.numel()
+    if a_ptr.numel() != N + 1 or a_val.dim() != 2 or a_val.shape[1] != a_nnz or (a_nnz > 1 and a_val.stride(1) != 1):
+        raise _capi.NativeLibraryError("fsai_lu_build: a_ptr must have N + 1 entries and the values be (B, %d) rows of "
+                                       "unit stride, got %s" % (a_nnz, tuple(a_val.shape)))
+    if check_pattern:
+        fsai_check_pattern(g_ptr, g_idx, N, cap=fsai_lu_max_row())
+    B = a_val.shape[0]
+    if out is None:
+        out = tuple(torch.zeros((B, g_nnz), dtype=a_val.dtype, device=a_val.device) for _ in range(2))
+    gl, w = out
+    for t in (gl, w):
+        if t.shape != (B, g_nnz) or t.dtype != a_val.dtype or not t.is_contiguous() or t.device != a_val.device:
+            raise _capi.NativeLibraryError("fsai_lu_build: the outputs must be contiguous (%d, %d) tensors" % (B, g_nnz))
+    if nfail is None:
+        nfail = torch.zeros((B,), dtype=torch.int32, device=a_val.device)
+    rc = call("xk_fsai_lu_build", a_val.dtype, ptr(a_ptr), ptr(a_idx), ptr(a_val), a_val.stride(0) if B > 1 else 0,
+              a_nnz, ptr(g_ptr), ptr(g_idx), ptr(gl), ptr(w), gl.stride(0) if B > 1 else 0, g_nnz, ptr(nfail), int(N),
+              B, raw=raw)
+    return rc if raw else (gl, w, nfail)

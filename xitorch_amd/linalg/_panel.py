@@ -16,6 +16,7 @@ copies for the native storage kinds; `PanelOperator` is the square case of the e
   SparseLinearOperator  -> xk_csr_mm     (fp32 / fp64 / complex64 / complex128 values; the adjoint on the pattern's
                                           CSC view, complex values conjugated by the kernel)
   FSAIOperator          -> xk_csr_mm twice (G, then G^H on G's CSC view) through a cached scratch panel (square only)
+  FSAILUOperator        -> xk_csr_mm twice (G_L, then W^H; the adjoint: W, then G_L^H) on the one pattern, same scratch
   anything else         -> the operator's own .mm/.rmm on the (.., N, p) strided view
 """
 import math
@@ -160,16 +161,17 @@ class RectPanelOperator:
 class PanelOperator(RectPanelOperator):
     """The square operator (*BA, N, N) of the eigensolvers and the Krylov solvers: the rectangular apply plus what only
     a square operator has -- the symmetric-storage kernels K1s / K1sw and the column-oriented K1 of a verified
-    symmetric matrix, the dropped `trans` of a Hermitian operator, FSAIOperator (kind "fsai"), `diagonal()`, the
+    symmetric matrix, the dropped `trans` of a Hermitian operator, FSAIOperator (kind "fsai"), FSAILUOperator (kind
+    "fsai_lu"), `diagonal()`, the
     two-stream `apply_on` and the event hooks of the measurements."""
 
     def __init__(self, A, bdims, Bt, N):
-        from xitorch_amd.linalg.precond import FSAIOperator
+        from xitorch_amd.linalg.precond import FSAIOperator, FSAILUOperator
         super().__init__(A, bdims, Bt)
         self.N = N
         self.symm = False
         self.symm_narrow = False
-        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded / csr / fsai)
+        self.last_kernel = None     # which panel kernel served the last native apply (K1s / K1w / K1wr / K1 / banded / csr / fsai / fsai_lu)
         self.events = None          # when a list: (start, end, p) HIP events around every native launch
         self.hermitian = bool(getattr(A, "is_hermitian", False))
         if self.kind == "dense":
@@ -192,6 +194,16 @@ class PanelOperator(RectPanelOperator):
             self.pat.csc()                    # the view of G^H, built here rather than in the first iteration
             self.vals = _csr_values(A.G)
             self._scratch = None              # G x; reallocated only when the column count grows
+        elif isinstance(A, FSAILUOperator) and _native(A.GL.values) and _native(A.W.values) and self.batch_ok:
+            # P = W^H G_L (adjoint flag: P^H = G_L^H W): two CSR products on the padded panels, one shared pattern
+            self.kind = "fsai_lu"
+            self.cplx = A.GL.values.is_complex()
+            self.adjoint = A.adjoint
+            self.pat = A.GL._pattern
+            self.pat.csc()
+            self.vals = _csr_values(A.GL)
+            self.vals_w = _csr_values(A.W)
+            self._scratch = None
 
     def diagonal(self):
         """diag(A) as a contiguous (nA, N) array (native operators only)."""
@@ -256,15 +268,19 @@ class PanelOperator(RectPanelOperator):
 
     def _native(self, X, out, trans):
         N = self.N
-        if self.kind == "fsai":
-            self.last_kernel = "fsai"
+        if self.kind in ("fsai", "fsai_lu"):
+            self.last_kernel = self.kind
             p = X.shape[1]
             if self._scratch is None or self._scratch.shape[0] != X.shape[0] or self._scratch.shape[1] < p or \
                     self._scratch.dtype != X.dtype:
                 self._scratch = torch.empty((X.shape[0], p, N), dtype=X.dtype, device=X.device)
             scr = self._scratch[:, :p]
-            K.csr_mm(self.pat, self.vals, X[:, :, :N], out=scr, trans=False)
-            K.csr_mm(self.pat, self.vals, scr, out=out[:, :, :N], trans=True)
+            first, second = self.vals, self.vals                   # fsai: G, then G^H
+            if self.kind == "fsai_lu":
+                # P = W^H G_L; the adjoint (the operator's flag, or the caller's trans, not both) is G_L^H W
+                first, second = (self.vals_w, self.vals) if trans != self.adjoint else (self.vals, self.vals_w)
+            K.csr_mm(self.pat, first, X[:, :, :N], out=scr, trans=False)
+            K.csr_mm(self.pat, second, scr, out=out[:, :, :N], trans=True)
         elif self.kind != "dense" or self.cplx:
             if self.kind != "dense":
                 self.last_kernel = self.kind                   # "csr" / "banded"

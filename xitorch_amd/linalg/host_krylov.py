@@ -256,7 +256,7 @@ def bicgstab(A, B, E=None, M=None, posdef=None, precond_l=None, precond_r=None, 
 
 
 def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-8, eps=1e-12, resid_calc_every=1,
-          restart=None, process_group=None, trace=None, **unused):
+          restart=None, process_group=None, trace=None, precond_r=None, **unused):
     """Un-restarted GMRES in host memory (reference: gmres, solve.py:326-433; real and complex operators — the
     reference's is real-only; `_coldot` conjugates its first argument, so the Hessenberg matrix of a complex operator
     is the complex one and `torch.linalg.lstsq` solves it as it stands): the same iterates, stopping rule and return
@@ -264,11 +264,16 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     the iterate minimises the residual over the k-dimensional Krylov space, the TRUE residual decides convergence and
     which iterate is the best one, at most min(nr, max_niter) - 1 Krylov vectors contribute.  The Hessenberg matrices
     of all systems are one batched tensor; the small least-squares problem is `torch.linalg.lstsq`, as in the
-    reference (:403).  `restart=m` (extension): GMRES(m), as in the native driver."""
+    reference (:403).  `restart=m` (extension): GMRES(m), as in the native driver.  `precond_r=P` (extension): right
+    preconditioning, w = A (P q_j) and x = x_base + P (Q y), as in the native driver."""
     calls["gmres"] += 1
     X0, prob, stop, max_niter = _setup(A, B, E, M, posdef, False, max_niter, rtol, atol, process_group, niter_factor=1)
     if X0 is not None:
         return X0
+    pr = _precond(precond_r)
+    if pr is not None and prob.normal:
+        raise ValueError("gmres: precond_r cannot be used when the normal equations are solved (posdef=False): a "
+                         "preconditioner of A is not one of A^H A")
     nr = A.shape[-1]
     msteps = min(nr, max_niter) - 1
     if restart is not None:
@@ -290,7 +295,7 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     for k in range(msteps):
         j = k - cyc0
         nsteps = k + 1
-        w = prob.apply(Q[j])
+        w = prob.apply(Q[j] if pr is None else pr(Q[j]))
         for i in range(j + 1):                                      # modified Gram-Schmidt (solve.py:391-393)
             hij = _coldot(Q[i], w)
             H[..., i, j] = hij.squeeze(-2)
@@ -305,9 +310,15 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         g = torch.zeros((*prob.bdims, prob.nc, j + 2, 1), dtype=prob.dtype)
         g[..., 0, 0] = beta.squeeze(-2)
         ycoef = torch.linalg.lstsq(H[..., :j + 2, :j + 1], g)[0]    # (*batch, nc, j+1, 1)
-        x = xbase
-        for i in range(j + 1):
-            x = x + Q[i] * ycoef[..., i, 0].unsqueeze(-2)
+        if pr is None:
+            x = xbase
+            for i in range(j + 1):
+                x = x + Q[i] * ycoef[..., i, 0].unsqueeze(-2)
+        else:
+            qy = Q[0] * ycoef[..., 0, 0].unsqueeze(-2)
+            for i in range(1, j + 1):
+                qy = qy + Q[i] * ycoef[..., i, 0].unsqueeze(-2)
+            x = xbase + pr(qy)
         rtrue = prob.rhs - prob.apply(x)
         mx, nbad = _status(_colnorm(rtrue), stop, process_group)
         if mx < best:                                               # solve.py:417-421

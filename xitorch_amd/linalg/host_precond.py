@@ -1,5 +1,5 @@
 """FSAI in torch ops: the pattern of G (every device) and its values for operators in host memory or of a dtype the HIP
-kernel does not serve.
+kernel does not serve; `fsai_lu_values` is the same for the unsymmetric form (two factors, pivoted LU per block).
 
 The values are the algorithm of xk_fsai_build (csrc/xk_fsai.hip) restated with batched library calls: the rows of G are
 grouped by their length m, the m x m blocks A[S_i, S_i] of a group are gathered at once, factored by
@@ -10,7 +10,7 @@ that bound the memory of the gathered blocks.
 """
 import torch
 
-__all__ = ["fsai_pattern", "fsai_values"]
+__all__ = ["fsai_pattern", "fsai_values", "fsai_lu_values"]
 
 _CHUNK_ELEMS = 1 << 22          # elements of the gathered blocks held at once
 
@@ -21,14 +21,16 @@ def _row_ptr(rows, N):
     return ptr
 
 
-def fsai_pattern(row_of, col, N, power=1, max_row=32):
+def fsai_pattern(row_of, col, N, power=1, max_row=32, full=False):
     """Pattern of G: row i takes the columns j <= i of row i of |A|^power — A's structure being its stored lower triangle
-    mirrored — plus i itself; a row longer than max_row keeps its max_row LARGEST columns.  -> (g_ptr (N+1,), g_idx)
-    int32, columns ascending and unique, the diagonal last in every row."""
+    mirrored (full=True, the unsymmetric FSAI: ALL its stored entries, both triangles, mirrored) — plus i itself; a row
+    longer than max_row keeps its max_row LARGEST columns.  -> (g_ptr (N+1,), g_idx) int32, columns ascending and unique,
+    the diagonal last in every row."""
     dev = col.device
     r, c = row_of.to(torch.int64), col.to(torch.int64)
-    low = c <= r
-    r, c = r[low], c[low]
+    if not full:
+        low = c <= r
+        r, c = r[low], c[low]
     ar = torch.arange(N, dtype=torch.int64, device=dev)
     keys = torch.unique(torch.cat([r * N + c, c * N + r, ar * N + ar]))          # sorted: by row, then by column
     i1, j1 = keys // N, keys % N
@@ -104,3 +106,65 @@ def fsai_values(a_row, a_col, a_val, g_ptr, g_idx, N):
             g_val[:, slot] = g.resolve_conj()
             nfail += bad.sum(1)
     return g_val, nfail
+
+
+def fsai_lu_values(a_row, a_col, a_val, g_ptr, g_idx, N):
+    """Values of the unsymmetric FSAI factors on the one pattern (g_ptr, g_idx) for the operator whose stored entries are
+    (a_row, a_col, a_val (nb, nnz)), the algorithm of xk_fsai_lu_build (csrc/xk_fsai_lu.hip) in batched library calls:
+    per row the full block A[S, S] (duplicates add up, unstored entries are zero), one `torch.linalg.lu_factor_ex`, then
+    A_SS u = e_m and A_SS^T g = e_m; row i of G_L is g / g_m with a unit diagonal, row i of W = G_U^H is conj(u).  A row
+    with a zero or non-finite pivot, a non-finite u or g, or g_m = 0 falls back to G_L[i, .] = e_i, G_U[., i] = e_i / a_ii
+    (e_i for a zero or non-finite a_ii).  -> (gl_val, w_val (nb, g_nnz), nfail (nb,) int64)."""
+    dev, dtype = a_val.device, a_val.dtype
+    nb = a_val.shape[0]
+    r, c = a_row.to(torch.int64), a_col.to(torch.int64)
+    ukeys, inv = torch.unique(r * N + c, return_inverse=True)
+    nu = ukeys.numel()
+    uval = torch.zeros((nb, nu), dtype=dtype, device=dev).index_add(1, inv, a_val)
+    gp, gi = g_ptr.to(torch.int64), g_idx.to(torch.int64)
+    lens = gp[1:] - gp[:-1]
+    gl_val = torch.zeros((nb, gi.numel()), dtype=dtype, device=dev)
+    w_val = torch.zeros((nb, gi.numel()), dtype=dtype, device=dev)
+    nfail = torch.zeros((nb,), dtype=torch.int64, device=dev)
+    zero, one = torch.zeros((), dtype=dtype, device=dev), torch.ones((), dtype=dtype, device=dev)
+    for m in torch.unique(lens).tolist():
+        rows_m = torch.nonzero(lens == m).reshape(-1)
+        am = torch.arange(m, dtype=torch.int64, device=dev)
+        e = torch.zeros((m, 1), dtype=dtype, device=dev)
+        e[-1] = 1
+        chunk = max(1, _CHUNK_ELEMS // (m * m * nb))
+        for s in range(0, rows_m.numel(), chunk):
+            slot = gp[rows_m[s:s + chunk]][:, None] + am                         # (nr, m) positions in the factors
+            S = gi[slot]
+            Q = S[:, :, None] * N + S[:, None, :]                                # key of A[S_r, S_c]
+            if nu:
+                p = torch.searchsorted(ukeys, Q.reshape(-1)).clamp_(max=nu - 1).reshape(Q.shape)
+                blk = torch.where(ukeys[p] == Q, uval[:, p], zero)
+            else:
+                blk = torch.zeros((nb, *Q.shape), dtype=dtype, device=dev)
+            aii = blk[..., m - 1, m - 1]
+            # a block with a non-finite entry is decided here (its pivots or its solutions are not finite either way):
+            # the library factorisation is not asked to work on NaN
+            sick = ~torch.isfinite(blk).all(-1).all(-1)
+            work = torch.where(sick[..., None, None], torch.eye(m, dtype=dtype, device=dev), blk)
+            LU, piv, info = torch.linalg.lu_factor_ex(work)
+            dg = torch.diagonal(LU, dim1=-2, dim2=-1)
+            bad = sick | (info != 0) | (dg == 0).any(-1) | ~torch.isfinite(dg).all(-1)
+            safe = torch.where(bad[..., None, None], torch.eye(m, dtype=dtype, device=dev), LU)
+            spiv = torch.where(bad[..., None], (am + 1).to(piv.dtype), piv)
+            eb = e.expand(nb, S.shape[0], m, 1)
+            u = torch.linalg.lu_solve(safe, spiv, eb).squeeze(-1)
+            g = torch.linalg.lu_solve(safe, spiv, eb, adjoint=True).squeeze(-1)  # A^H x = e_m: x = conj(g)
+            g = g.conj()
+            gm = g[..., m - 1]
+            bad = bad | ~torch.isfinite(u).all(-1) | ~torch.isfinite(g).all(-1) | (gm == 0)
+            gl = g / torch.where(bad, one, gm)[..., None]
+            gl[..., m - 1] = 1
+            ok_d = (aii != 0) & torch.isfinite(aii)
+            unit = torch.zeros_like(gl)
+            unit[..., m - 1] = 1
+            wfb = unit * (1 / torch.where(ok_d, aii, one)).conj()[..., None]
+            gl_val[:, slot] = torch.where(bad[..., None], unit, gl).resolve_conj()
+            w_val[:, slot] = torch.where(bad[..., None], wfb, u.conj()).resolve_conj()
+            nfail += bad.sum(1)
+    return gl_val, w_val, nfail

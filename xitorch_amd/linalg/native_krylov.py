@@ -532,7 +532,7 @@ class _GmresState:
 
 
 def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-8, eps=1e-12,
-          resid_calc_every=1, restart=None, process_group=None, trace=None, **unused):
+          resid_calc_every=1, restart=None, process_group=None, trace=None, precond_r=None, **unused):
     r"""
     Solve the linear equations using the Generalised minimal residual method on HIP kernels
     (reference: gmres, xitorch/_impls/linalg/solve.py:326-433).  Real and complex operators (extension: the reference's
@@ -581,6 +581,12 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         bounds the total number of steps.
     process_group: torch.distributed group or None
         (extension) batch-sharded multi-GPU run: the stopping test is all-reduced over the group
+    precond_r: LinearOperator or None
+        (extension) right preconditioner ``P``: the Krylov space is that of ``A P`` (one more panel apply per Arnoldi
+        step, ``w = A (P q_j)``) and the iterate is ``x_base + P (Q y)``; the residual of the right-preconditioned
+        system is the true residual of the original one, so the stopping rule, the best-iterate rule and every other
+        option are untouched.  Refused (``ValueError``) when the problem resolves to the normal equations: a
+        preconditioner of ``A`` is not one of ``A^H A``.  ``linalg.fsai_lu(A)`` makes one for a sparse ``A``.
 
     With ``E`` the reference returns its column-swapped work layout ``(ncols, *batch, nr, 1)`` without undoing the
     swap (:432, and fails for more than one column); this function returns ``(*batch, nr, ncols)`` like every other
@@ -588,10 +594,14 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
     """
     run = _Run("gmres", A, B, E, M, dict(
         posdef=posdef, max_niter=max_niter, rtol=rtol, atol=atol, eps=eps, resid_calc_every=resid_calc_every,
-        restart=restart, process_group=process_group, trace=trace), posdef, False, niter_factor=1)
+        restart=restart, process_group=process_group, trace=trace, precond_r=precond_r), posdef, False, niter_factor=1)
     if run.X is not None:
         return run.X
     prob, kr, stop, max_niter = run.prob, run.kr, run.stop, run.max_niter
+    pr = _precond(precond_r, prob)
+    if pr is not None and prob.normal:
+        raise ValueError("gmres: precond_r cannot be used when the normal equations are solved (posdef=False): a "
+                         "preconditioner of A is not one of A^H A")
     nr = A.shape[-1]
     S, N, ld = prob.S, prob.N, prob.ld
     dtype, dev = prob.dtype, prob.device
@@ -631,6 +641,7 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
         status4 = torch.zeros((4,), dtype=torch.float64, device=dev)
         tmp = prob.new()
         rtrue = prob.new()
+        pq = prob.new() if pr is not None else None                  # P q_j, and Q y before P is applied to it
 
         def status_of(Prr, nblk, slot):
             call("xk_kry_status", kr.rdtype, ptr(Prr), ptr(stop), ptr(kr.rnorm), ptr(status4[2 * slot:]), S, nblk)
@@ -639,10 +650,13 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
             """x = Q y with R y = g (the reference's lstsq solution, :403-410), r = B - A x (:414): partials -> Ptrue"""
             call("xk_gmres_solve", dtype, ptr(st.R), ptr(st.g), ptr(st.ycoef), st.ycoef.stride(0), S, kd, st.hcap)
             x = xbufs[cur_i]
+            qy = x if pr is None else pq.reshape(S, 1, ld)
             if prob.cplx:
-                K.lincomb_c(st.Q, st.ycoef, x, kd, 1, alpha=1.0, beta=0.0, N=N)
+                K.lincomb_c(st.Q, st.ycoef, qy, kd, 1, alpha=1.0, beta=0.0, N=N)
             else:
-                K.lincomb(st.Q, st.ycoef, x, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
+                K.lincomb(st.Q, st.ycoef, qy, kd, 1, coef_layout="ca", alpha=1.0, beta=0.0)
+            if pr is not None:
+                pr.apply(pq, x.reshape(prob.Bt, prob.nc, ld))                  # x = P (Q y)
             if x_base is not None:
                 x.add_(x_base)
             prob.apply(x.reshape(prob.Bt, prob.nc, ld), tmp)
@@ -662,7 +676,15 @@ def gmres(A, B, E=None, M=None, posdef=None, max_niter=None, rtol=1e-6, atol=1e-
             Q = st.Q
             # w = A q_j (solve.py:390) straight into basis row j+1; with a shift E the fused shift kernel wants
             # contiguous (S, ld) arrays, so q_j / w pass through two contiguous buffers (O(N) copies)
-            if prob.E is None:
+            if pr is not None:
+                # right preconditioning: w = A (P q_j), through the contiguous scratch panel
+                pr.apply(Q[:, j].reshape(prob.Bt, prob.nc, ld), pq)
+                if prob.E is None:
+                    prob.apply(pq, Q[:, j + 1].reshape(prob.Bt, prob.nc, ld))
+                else:
+                    prob.apply(pq, tmp)
+                    Q[:, j + 1].copy_(tmp.reshape(S, ld))
+            elif prob.E is None:
                 prob.apply(Q[:, j].reshape(prob.Bt, prob.nc, ld), Q[:, j + 1].reshape(prob.Bt, prob.nc, ld))
             else:
                 rtrue.reshape(S, ld).copy_(Q[:, j])

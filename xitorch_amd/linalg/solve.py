@@ -35,7 +35,9 @@ def solve(A, B, E=None, M=None, bck_options={}, method=None, **fwd_options):
         plugs in a user method.
     **fwd_options
         Method-specific options.  For ``"cg"`` and ``"minres"`` the option ``precond`` (here or in ``bck_options``)
-        also takes the string ``"fsai"``: ``linalg.fsai(A)`` with its defaults, for a ``SparseLinearOperator`` ``A``
+        also takes the string ``"fsai"``: ``linalg.fsai(A)`` with its defaults, for a ``SparseLinearOperator`` ``A``.
+        For ``"gmres"`` (``precond_r``) and ``"bicgstab"`` (``precond_l`` / ``precond_r``) the string ``"fsai_lu"``
+        builds ``linalg.fsai_lu(A)``, in the backward solve ``linalg.fsai_lu(A).H``
     """
     assert_runtime(A.shape[-1] == A.shape[-2], "The linear operator A must have a square shape")
     assert_runtime(A.shape[-1] == B.shape[-2], "Mismatch shape of A & B (A: %s, B: %s)" % (A.shape, B.shape))
@@ -101,11 +103,18 @@ class _SolveFunction(torch.autograd.Function):
                     "minres": nk.minres,
                     "scipy_gmres": nk.scipy_gmres,
                 }
-                if isinstance(config.get("precond"), str) and method in ("cg", "minres"):
-                    # a named preconditioner, built once per call from the operator as it is now (the backward solve
-                    # comes through here again with bck_options)
-                    from xitorch_amd.linalg.precond import named_preconditioner
-                    config["precond"] = named_preconditioner(config["precond"], A, method)
+                # a named preconditioner, built once per call from the operator as it is now (the backward solve
+                # comes through here again with bck_options, and with A.H)
+                named = {"cg": ("precond",), "minres": ("precond",), "gmres": ("precond_r",),
+                         "bicgstab": ("precond_l", "precond_r")}.get(method, ())
+                built = {}
+                for key in named:
+                    if isinstance(config.get(key), str):
+                        from xitorch_amd.linalg.precond import named_preconditioner
+                        name = config[key]
+                        if name not in built:
+                            built[name] = named_preconditioner(name, A, method)
+                        config[key] = built[name]
                 x = get_method("solve", methods, method)(A, B, E, M, **config)
         ctx.e_is_none = E is None
         ctx.A, ctx.M, ctx.na = A, M, na
